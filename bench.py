@@ -20,6 +20,12 @@ the reference times in its diagnostics loop: theta update, link/value/
 distortion updates, partition reassignment, migration all-to-all, and the
 summary all-reduce. Sample/diagnostic file writes are excluded (the
 reference amortizes them 1/thinningInterval = 1/10; checkpointing off).
+
+A plain run does only that. ``--full`` adds the secondary figures (ESS and
+ESS/sec of the timed region, the sampler's path counters);
+``--dump-outputs DIR`` writes the chain state the last timed sweep produced
+as ``DIR/<name>.npy`` so two builds can be compared output for output (the
+data and the chain are fully determined by the arguments).
 """
 
 from __future__ import annotations
@@ -76,6 +82,51 @@ def build_cache_and_records(total_records, seed, schema="rldata", num_files=1):
     return cache, rec_values, rec_files
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, state, loglik_series, nobs_series, rank=0, world=1):
+    """Write what the last timed sweep left in ``state`` as DIR/<name>.npy.
+
+    Per-record arrays are put in global-record-id order and entities are named
+    by the smallest record id linked to them, so the files do not depend on
+    the engine's internal row order or entity numbering. Everything is
+    float64 (the ids are far below 2^53). Per-record arrays larger than the
+    byte budget are cut down to a fixed, seeded sample of records; the
+    sampled ids are written alongside.
+    """
+    os.makedirs(dirname, exist_ok=True)
+    R, A = state.rec_values.shape
+    order = np.argsort(state.rec_gid, kind="stable")
+    small = {
+        "dist_probs": np.asarray(state.dist_probs.probs),
+        "summary_scalars": np.array([state.iteration, state.summary.log_likelihood,
+                                     state.summary.num_isolates]),
+        "summary_agg_distortions": state.summary.agg_distortions,
+        "summary_rec_distortions": state.summary.rec_distortions,
+        "loglik_series": loglik_series,
+        "num_observed_series": nobs_series,
+    }
+    budget = DUMP_MAX_BYTES - sum(8 * np.size(v) for v in small.values())
+    max_rows = max(1, budget // (8 * (2 * A + 2)))
+    if R > max_rows:
+        pick = np.sort(np.random.default_rng(0).choice(R, size=max_rows, replace=False))
+        order = order[pick]
+    # cluster label: smallest global record id linked to the same entity
+    ent_min_gid = np.full(state.num_entities, np.iinfo(np.int64).max, dtype=np.int64)
+    np.minimum.at(ent_min_gid, state.rec_ent, state.rec_gid)
+    per_record = {
+        "rec_gid": state.rec_gid[order],
+        "rec_cluster": ent_min_gid[state.rec_ent[order]],
+        "rec_entity_values": state.ent_values[state.rec_ent[order]],
+        "rec_distortions": state.rec_dist[order],
+    }
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for name, arr in {**small, **per_record}.items():
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"),
+                np.ascontiguousarray(arr, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -98,6 +149,12 @@ def main():
     ap.add_argument("--init-state", default=None, metavar="DIR",
                     help="resume the chain from a saved state instead of "
                          "deterministic init")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed sweeps, write the chain state the "
+                         "last sweep produced as DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true",
+                    help="also report the secondary figures: ESS and ESS/sec of "
+                         "the timed region and the sampler's path counters")
     args = ap.parse_args()
 
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -219,14 +276,20 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.cpu())
 
-    if rank == 0 and getattr(engine, "_heavy_stats", None) is not None:
+    if args.dump_outputs:
+        if hasattr(engine, "sync_state"):
+            engine.sync_state(state)
+        dump_outputs(args.dump_outputs, state, loglik_series, nobs_series,
+                     rank=rank, world=world)
+
+    if args.full and rank == 0 and getattr(engine, "_heavy_stats", None) is not None:
         hs = engine._heavy_stats.cpu().numpy()
         if hs[3]:
             print(f"[bench] heavy link sampler: {int(hs[3])} records, "
                   f"{int(hs[2])} similar-set visits, {int(hs[0])} A* iterations, "
                   f"{int(hs[1])} full-scan fallbacks (all sweeps)", file=sys.stderr)
 
-    if rank == 0 and getattr(engine, "_value_stats", None) is not None:
+    if args.full and rank == 0 and getattr(engine, "_value_stats", None) is not None:
         vs = engine._value_stats.cpu().numpy()
         print(f"[bench] value k>=2: {int(vs[0])} pairs ({int(vs[1])} hash / "
               f"{int(vs[2])} merge / {int(vs[6])} k>Kc), sum_entries={int(vs[3])} "
@@ -246,11 +309,13 @@ def main():
     if rank == 0:
         value = args.steps / elapsed
         # ESS/sec secondary metric (BASELINE.json): Geyer initial-monotone
-        # ESS of the per-sweep summary series over the timed region
-        from dblink_amd.analysis.diagnostics import ess as _ess
+        # ESS of the per-sweep summary series over the timed region (--full)
+        ess_loglik = ess_nobs = None
+        if args.full and args.steps >= 50:
+            from dblink_amd.analysis.diagnostics import ess as _ess
 
-        ess_loglik = _ess(loglik_series) if args.steps >= 50 else None
-        ess_nobs = _ess(nobs_series) if args.steps >= 50 else None
+            ess_loglik = _ess(loglik_series)
+            ess_nobs = _ess(nobs_series)
         ess_per_sec = (
             min(ess_loglik, ess_nobs) / elapsed if ess_loglik is not None else None
         )

@@ -77,6 +77,10 @@ def _run_workers(script, world=2, timeout=600):
         MASTER_PORT=str(29500 + os.getpid() % 1000),
         WORLD_SIZE=str(world),
         GLOO_SOCKET_IFNAME="lo",
+        # these are CPU-engine pseudocluster tests: keep workers that take the
+        # backend from the environment on gloo even where a GPU is visible
+        # (RCCL rejects several ranks sharing one device)
+        DBLINK_BACKEND="gloo",
     )
     procs = []
     for r in range(world):

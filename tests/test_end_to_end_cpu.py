@@ -309,21 +309,29 @@ def test_summarize_smpc_quantity(tmp_path):
     assert sum(len(c) for c in clusters) == 120
 
 
-REFERENCE_RLDATA500 = "/root/reference/examples/RLdata500.csv"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def _golden_csv(name, tmp_path):
+    """Unpack tests/golden/<name>.gz (stored compressed) into tmp_path."""
+    import gzip
+
+    dst = tmp_path / name
+    with gzip.open(os.path.join(GOLDEN, name + ".gz"), "rb") as f:
+        dst.write_bytes(f.read())
+    return str(dst)
 
 
 @pytest.mark.slow
-@pytest.mark.skipif(not os.path.exists(REFERENCE_RLDATA500),
-                    reason="reference RLdata500 not available")
 def test_real_rldata500_with_reference_config(tmp_path):
     """THE parity benchmark: the reference's shipped RLdata500 dataset with
     its RLdata500.conf VERBATIM (only file paths redirected). The d-blink
     methodology reports ~0.9 pairwise F1 on this dataset; a correct
     implementation must land there."""
-    src = open("/root/reference/examples/RLdata500.conf").read()
+    src = open(os.path.join(GOLDEN, "RLdata500.conf")).read()
     out = str(tmp_path / "rl500")
     conf = (src
-            .replace("./examples/RLdata500.csv", REFERENCE_RLDATA500)
+            .replace("./examples/RLdata500.csv", _golden_csv("RLdata500.csv", tmp_path))
             .replace("./examples/RLdata500_results/", out + "/"))
     conf_path = tmp_path / "rl500.conf"
     conf_path.write_text(conf)
@@ -340,16 +348,11 @@ def test_real_rldata500_with_reference_config(tmp_path):
     assert ari > 0.8, txt
 
 
-REFERENCE_RLDATA10000 = "/root/reference/examples/RLdata10000.csv"
-
-
 @pytest.mark.slow
 # runs in the default suite since the native CPU sweeps brought it from
 # ~7 min to ~25 s; DBLINK_SLOW_TESTS=0 opts out on very slow machines
 @pytest.mark.skipif(os.environ.get("DBLINK_SLOW_TESTS") == "0",
                     reason="opted out with DBLINK_SLOW_TESTS=0")
-@pytest.mark.skipif(not os.path.exists(REFERENCE_RLDATA10000),
-                    reason="reference RLdata10000 not available")
 def test_real_rldata10000_published_quality(tmp_path):
     """The reference's shipped RLdata10000 dataset with its RLdata10000.conf,
     distortion prior tightened to Beta(10, 10000) and a 4,000-iteration
@@ -357,10 +360,11 @@ def test_real_rldata10000_published_quality(tmp_path):
     operating point even at 21k iterations — FP analysis in BENCH.md).
     The d-blink methodology reports ~0.94 pairwise F1 for this dataset;
     measured 0.944 here."""
-    src = open("/root/reference/examples/RLdata10000.conf").read()
+    src = open(os.path.join(GOLDEN, "RLdata10000.conf")).read()
     out = str(tmp_path / "rl10k")
     conf = (src
-            .replace("./examples/RLdata10000.csv", REFERENCE_RLDATA10000)
+            .replace("./examples/RLdata10000.csv",
+                     _golden_csv("RLdata10000.csv", tmp_path))
             .replace("./examples/RLdata10000_results/", out + "/")
             .replace("/tmp/spark_checkpoint/", str(tmp_path / "ckpt") + "/")
             .replace("lowDistortion : {alpha : 10.0, beta : 1000.0}",
