@@ -1,24 +1,23 @@
 // CDNA4 (gfx950) HIP kernels for the partitioned Gibbs sweep.
 //
-// Kernel inventory (SURVEY.md §2.4 K-list):
-//   K3+K4+K5  link_update           — posting-list intersection + per-candidate
-//                                     log-weights + fused Gumbel-max draw
-//             link_update_dense     — PCG-II collapsed / Gibbs-Sequential dense
-//                                     variants (LDS-tiled over entity values)
-//   K6        value_update          — per-(entity, attribute) collapsed /
-//                                     non-collapsed value draw with sparse
-//                                     perturbation weights merged in an LDS
-//                                     hash table; alias-table base draws
-//             value_update_seq      — brute-force dense-domain variant
-//   K7        distortion_update     — element-wise Bernoulli resample (Philox)
-//   K8        summary_loglik        — f64 block/atomic reduction of the
-//                                     log-likelihood terms
-//   K9a       kd_descent            — flat KD-tree partition reassignment
-//   K1 (GPU)  sim_pairs count/fill  — banded Levenshtein domain sweep
+// Kernel inventory (K-numbers as in STATUS.md "§2.2 / §2.4 kernels"):
+//   K4+K5  link_update{,_small,_heavy}_kernel — wave / thread / hierarchical
+//              A* link draw, one shared candidate-scoring core (link_* below)
+//          link_update_dense_kernel — PCG-II / Gibbs-Sequential partition scan
+//   K6     value_base_draw (k=0), value_update_k1, _kd1, _kd2,
+//              value_update_kernel_t<VMODE> (LDS hash / union merge), _seq
+//   K7     distortion_update_kernel — Bernoulli resample, loglik fused in
+//   K8     summary_loglik / summary_counts / summary_finalize
+//   K3     build_keys, postings_hist / _scatter (counting sort), cand_ranges,
+//              build_ekeys_stable (+ rocprim radix sort), classify_modes
+//   --     mfma_score / scalar_score — matrix-core scoring experiment
+//   K9     kd_descent_kernel — flat KD-tree partition reassignment
+//   K1     sim_pairs_kernel — bit-parallel Levenshtein domain sweep
 //
-// One wave (64 lanes) owns one record / one (entity, attribute) pair; block
-// size 256 = 4 waves. All categorical draws use Gumbel-max with Philox
-// counter RNG (common.h), so results are independent of scheduling order.
+// Wave kernels give one wave (64 lanes) a record or an (entity, attribute)
+// pair, 4 waves per block; thread kernels give one lane an item. All
+// categorical draws use Gumbel-max with Philox counter RNG (common.h), so
+// results are independent of scheduling order.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
@@ -114,6 +113,127 @@ __device__ inline float simh_lookup(const int32_t* kh, const float* vh,
 }
 
 // ---------------------------------------------------------------------------
+// Candidate-scoring core shared by the link kernels. The wave, thread and
+// heavy paths must draw the SAME entity for a record (routing between them
+// is a performance decision), so classification, base selection, the
+// equality check and the f32 log-weight each exist once, here.
+// ---------------------------------------------------------------------------
+
+// Device-side {seed, iteration} override: graph replays read both from ctrl.
+DBL_D void ctrl_override(const int64_t* __restrict__ ctrl, uint64_t& seed,
+                         uint32_t& iteration) {
+  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
+}
+
+// Attribute classification as BITMASKS, not arrays: runtime-indexed local
+// arrays spill to scratch (measured 208 B/lane = a scratch round-trip per
+// membership probe), and so do reference out-parameters here. nd = observed
+// non-distorted, od = observed distorted and non-constant (constant od attrs
+// scale all weights equally and cancel under normalization).
+struct LinkMasks { uint32_t nd, od; };
+
+DBL_D LinkMasks link_classify(const int32_t* __restrict__ rec_values,
+                              const uint8_t* __restrict__ rec_dist,
+                              const uint8_t* __restrict__ attr_const,
+                              int64_t r, int A) {
+  uint32_t nd_mask = 0, od_mask = 0;
+  for (int a = 0; a < A; ++a) {
+    const int32_t x = rec_values[r * A + a];
+    if (x < 0) continue;
+    if (!rec_dist[r * A + a]) nd_mask |= 1u << a;
+    else if (!attr_const[a]) od_mask |= 1u << a;
+  }
+  return {nd_mask, od_mask};
+}
+
+struct LinkBase {
+  int64_t lo, n;        // candidate range to enumerate
+  uint32_t check_mask;  // nd attrs every candidate must still be checked on
+  bool postings;        // range indexes postings[]; else it is entity ids
+};
+
+// base = smallest candidate list among nd attrs and (optional) const-pair
+// pseudo slots; a pair base implies both constituents match, but every nd
+// single must still be value-checked (check_mask keeps them all). Without
+// any nd attr the base is the record's whole partition.
+DBL_D LinkBase link_select_base(const int64_t* __restrict__ cand_lo,
+                                const int64_t* __restrict__ cand_hi,
+                                const int32_t* __restrict__ pair_a1,
+                                const int32_t* __restrict__ pair_a2, int NP,
+                                const int32_t* __restrict__ rec_part,
+                                const int64_t* __restrict__ ent_ptr,
+                                int64_t r, int A, uint32_t nd_mask) {
+  const int T = A + NP;
+  int base_attr = -1;
+  LinkBase b{0, INT64_MAX, 0, true};
+  for (uint32_t m = nd_mask; m;) {
+    const int a = __ffs(m) - 1;
+    m &= m - 1;
+    const int64_t lo = cand_lo[r * T + a], n = cand_hi[r * T + a] - lo;
+    if (n < b.n) { b.n = n; b.lo = lo; base_attr = a; }
+  }
+  for (int t = 0; t < NP; ++t) {
+    const int a1 = pair_a1[t], a2 = pair_a2[t];
+    if (((nd_mask >> a1) & 1u) == 0 || ((nd_mask >> a2) & 1u) == 0) continue;
+    const int64_t lo = cand_lo[r * T + A + t], n = cand_hi[r * T + A + t] - lo;
+    if (n < b.n) { b.n = n; b.lo = lo; base_attr = -1; }
+  }
+  if (nd_mask == 0) {
+    const int32_t p = rec_part[r];
+    b.lo = ent_ptr[p];
+    b.n = ent_ptr[p + 1] - b.lo;
+    b.postings = false;
+  }
+  b.check_mask = base_attr >= 0 ? (nd_mask & ~(1u << base_attr)) : nd_mask;
+  return b;
+}
+
+// Entity e equals record r on every attribute in mask.
+DBL_D bool link_matches(const int32_t* __restrict__ ent_values,
+                        const int32_t* __restrict__ rec_values, int64_t e,
+                        int64_t r, int A, uint32_t mask) {
+  for (uint32_t m = mask; m;) {
+    const int a = __ffs(m) - 1;
+    m &= m - 1;
+    if (ent_values[e * A + a] != rec_values[r * A + a]) return false;
+  }
+  return true;
+}
+
+// f32 observed-distorted log-weight of entity e for record r:
+// sum over od attrs (ascending) of log_norm(y) + sim(x, y), each term added
+// as one f32 sum — the order every path must share to stay bitwise equal.
+// sim(a, row, y) is the lookup (staged or global); attribute a_given, if
+// any, takes sim_given instead (the heavy S_r scan enumerates by sim row).
+template <class Sim>
+DBL_D float link_logw(const int32_t* __restrict__ ent_values,
+                      const int32_t* __restrict__ rec_values,
+                      const float* __restrict__ log_norm,
+                      const int64_t* __restrict__ voff, int64_t e, int64_t r,
+                      int A, uint32_t od_mask, const Sim& sim,
+                      int a_given = -1, float sim_given = 0.0f) {
+  float logw = 0.0f;
+  for (uint32_t m = od_mask; m;) {
+    const int a = __ffs(m) - 1;
+    m &= m - 1;
+    const int32_t y = ent_values[e * A + a];
+    logw += log_norm[voff[a] + y] +
+            (a == a_given ? sim_given
+                          : sim(a, voff[a] + rec_values[r * A + a], y));
+  }
+  return logw;
+}
+
+// Empty candidate set (state invariant violated): count it, keep the link.
+DBL_D long long link_winner_or_keep(long long best_e,
+                                    const int64_t* __restrict__ rec_ent_in,
+                                    int64_t r, int* __restrict__ error_count) {
+  if (best_e >= 0) return best_e;
+  atomicAdd(error_count, 1);
+  return rec_ent_in[r];
+}
+
+// ---------------------------------------------------------------------------
 // K3+K4+K5: link update (PCG-I / Gibbs indexed path)
 //
 // Posting lists are used ONLY to enumerate the smallest candidate set;
@@ -155,48 +275,14 @@ __global__ void link_update_kernel(
   int64_t r = (int64_t)blockIdx.x * (blockDim.x / WAVE) + wid;
   if (r >= R) return;
   if (small_mask != nullptr && small_mask[r]) return;
-  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
+  ctrl_override(ctrl, seed, iteration);
 
-  // Attribute classification as BITMASKS, not arrays: runtime-indexed local
-  // arrays spill to scratch (measured 208 B/lane = a scratch round-trip per
-  // membership probe). All rec_values/voff reads below are wave-uniform, so
-  // they compile to scalar-cache loads and cost nothing per candidate.
-  // Constant observed-distorted attrs scale all weights equally and cancel
-  // under normalization, so od_mask keeps only non-constant ones.
-  const int T = A + NP;
-  uint32_t nd_mask = 0, od_mask = 0;
-  for (int a = 0; a < A; ++a) {
-    const int32_t x = rec_values[r * A + a];
-    if (x < 0) continue;
-    if (!rec_dist[r * A + a]) nd_mask |= 1u << a;
-    else if (!attr_const[a]) od_mask |= 1u << a;
-  }
-  // base = smallest candidate list among nd attrs and (optional) const-pair
-  // pseudo slots; a pair base implies both constituents match, but every nd
-  // single must still be value-checked (check_mask keeps them all).
-  int base_attr = -1;
-  int64_t base_lo = 0, base_n = INT64_MAX;
-  for (uint32_t m = nd_mask; m;) {
-    const int a = __ffs(m) - 1;
-    m &= m - 1;
-    const int64_t lo = cand_lo[r * T + a], n = cand_hi[r * T + a] - lo;
-    if (n < base_n) { base_n = n; base_lo = lo; base_attr = a; }
-  }
-  for (int t = 0; t < NP; ++t) {
-    const int a1 = pair_a1[t], a2 = pair_a2[t];
-    if (((nd_mask >> a1) & 1u) == 0 || ((nd_mask >> a2) & 1u) == 0) continue;
-    const int64_t lo = cand_lo[r * T + A + t], n = cand_hi[r * T + A + t] - lo;
-    if (n < base_n) { base_n = n; base_lo = lo; base_attr = -1; }
-  }
-  bool base_postings = true;
-  if (nd_mask == 0) {
-    const int32_t p = rec_part[r];
-    base_lo = ent_ptr[p];
-    base_n = ent_ptr[p + 1] - base_lo;
-    base_postings = false;
-  }
-  const uint32_t check_mask =
-      base_attr >= 0 ? (nd_mask & ~(1u << base_attr)) : nd_mask;
+  // All rec_values/voff reads below are wave-uniform, so they compile to
+  // scalar-cache loads and cost nothing per candidate.
+  const auto [nd_mask, od_mask] =
+      link_classify(rec_values, rec_dist, attr_const, r, A);
+  const LinkBase base = link_select_base(cand_lo, cand_hi, pair_a1, pair_a2,
+                                         NP, rec_part, ent_ptr, r, A, nd_mask);
 
   const uint64_t gid = (uint64_t)rec_gid[r];
   // stage this record's od-attr sim rows into LDS when the scan is long
@@ -204,128 +290,71 @@ __global__ void link_update_kernel(
   uint64_t logpk = 0, offpk = 0;
   int32_t* simh_k = simh_k_s[wid];
   float* simh_v = simh_v_s[wid];
-  if (simh_on && od_mask && base_n * __popc(od_mask) >= 32)
+  if (simh_on && od_mask && base.n * __popc(od_mask) >= 32)
     simh_stage(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, od_mask, logpk, offpk);
+  const auto sim = [&](int a, int64_t row, int32_t y) {
+    return simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr, csr_col,
+                       csr_sim, row, y);
+  };
   float best_score = -INFINITY;
   long long best_e = -1;
-  for (int64_t i = lane; i < base_n; i += WAVE) {
-    int32_t e = base_postings ? postings[base_lo + i] : (int32_t)(base_lo + i);
-    bool ok = true;
-    for (uint32_t m = check_mask; m;) {
-      const int a = __ffs(m) - 1;
-      m &= m - 1;
-      if (ent_values[(int64_t)e * A + a] != rec_values[r * A + a]) {
-        ok = false;
-        break;
-      }
-    }
-    if (!ok) continue;
-    float logw = 0.0f;
-    for (uint32_t m = od_mask; m;) {
-      const int a = __ffs(m) - 1;
-      m &= m - 1;
-      const int32_t y = ent_values[(int64_t)e * A + a];
-      logw += log_norm[voff[a] + y] +
-              simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr,
-                          csr_col, csr_sim, voff[a] + rec_values[r * A + a], y);
-    }
-    float g = gumbel_from_uniform(
-        philox_uniform(seed, iteration, PH_LINK, gid, (uint32_t)e));
-    float score = logw + g;
-    if (score > best_score) { best_score = score; best_e = e; }
-  }
-  wave_argmax(best_score, best_e);
-  if (lane == 0) {
-    if (best_e < 0) {  // empty candidate set: state invariant violated
-      atomicAdd(error_count, 1);
-      best_e = rec_ent_in[r];
-    }
-    rec_ent_out[r] = best_e;
-  }
-}
-
-// Thread-per-record link update for records whose smallest candidate list is
-// short (the common case once clusters localize): one thread walks the
-// intersection serially — 64x fewer wave slots than the wave path.
-__global__ void link_update_small_kernel(
-    const uint8_t* __restrict__ small_mask, int64_t n_recs,
-    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
-    const int64_t* __restrict__ rec_gid, const int64_t* __restrict__ cand_lo,
-    const int64_t* __restrict__ cand_hi, const int32_t* __restrict__ postings,
-    const int32_t* __restrict__ ent_values, const float* __restrict__ log_norm,
-    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
-    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
-    const uint8_t* __restrict__ attr_const,
-    const int32_t* __restrict__ pair_a1,
-    const int32_t* __restrict__ pair_a2, int NP, int A, uint64_t seed,
-    uint32_t iteration, const int64_t* __restrict__ ctrl,
-    int64_t* __restrict__ rec_ent_out,
-    const int64_t* __restrict__ rec_ent_in, int* __restrict__ error_count) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= n_recs) return;
-  if (small_mask[idx] != 1) return;
-  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
-  const int64_t r = idx;
-
-  // Bitmask classification (see link_update_kernel: local arrays spill)
-  const int T = A + NP;
-  uint32_t nd_mask = 0, od_mask = 0;
-  for (int a = 0; a < A; ++a) {
-    const int32_t x = rec_values[r * A + a];
-    if (x < 0) continue;
-    if (!rec_dist[r * A + a]) nd_mask |= 1u << a;
-    else if (!attr_const[a]) od_mask |= 1u << a;
-  }
-  int base_attr = -1;
-  int64_t base_lo = 0, base_sz = INT64_MAX;
-  for (uint32_t m = nd_mask; m;) {
-    const int a = __ffs(m) - 1;
-    m &= m - 1;
-    const int64_t lo = cand_lo[r * T + a], n = cand_hi[r * T + a] - lo;
-    if (n < base_sz) { base_sz = n; base_lo = lo; base_attr = a; }
-  }
-  for (int t = 0; t < NP; ++t) {
-    const int a1 = pair_a1[t], a2 = pair_a2[t];
-    if (((nd_mask >> a1) & 1u) == 0 || ((nd_mask >> a2) & 1u) == 0) continue;
-    const int64_t lo = cand_lo[r * T + A + t], n = cand_hi[r * T + A + t] - lo;
-    if (n < base_sz) { base_sz = n; base_lo = lo; base_attr = -1; }
-  }
-  const uint32_t check_mask =
-      base_attr >= 0 ? (nd_mask & ~(1u << base_attr)) : nd_mask;
-  const uint64_t gid = (uint64_t)rec_gid[r];
-  float best_score = -INFINITY;
-  long long best_e = -1;
-  for (int64_t i = base_lo; i < base_lo + base_sz; ++i) {
-    const int32_t e = postings[i];
-    bool ok = true;
-    for (uint32_t m = check_mask; m;) {
-      const int a = __ffs(m) - 1;
-      m &= m - 1;
-      if (ent_values[(int64_t)e * A + a] != rec_values[r * A + a]) {
-        ok = false;
-        break;
-      }
-    }
-    if (!ok) continue;
-    float logw = 0.0f;
-    for (uint32_t m = od_mask; m;) {
-      const int a = __ffs(m) - 1;
-      m &= m - 1;
-      const int32_t y = ent_values[(int64_t)e * A + a];
-      logw += log_norm[voff[a] + y] +
-              sim_lookup(csr_row_ptr, csr_col, csr_sim,
-                         voff[a] + rec_values[r * A + a], y);
-    }
+  for (int64_t i = lane; i < base.n; i += WAVE) {
+    int32_t e = base.postings ? postings[base.lo + i] : (int32_t)(base.lo + i);
+    if (!link_matches(ent_values, rec_values, e, r, A, base.check_mask)) continue;
+    const float logw =
+        link_logw(ent_values, rec_values, log_norm, voff, e, r, A, od_mask, sim);
     const float g = gumbel_from_uniform(
         philox_uniform(seed, iteration, PH_LINK, gid, (uint32_t)e));
     if (logw + g > best_score) { best_score = logw + g; best_e = e; }
   }
-  if (best_e < 0) {
-    atomicAdd(error_count, 1);
-    best_e = rec_ent_in[r];
+  wave_argmax(best_score, best_e);
+  if (lane == 0)
+    rec_ent_out[r] = link_winner_or_keep(best_e, rec_ent_in, r, error_count);
+}
+
+// Thread-per-record link update for records whose smallest candidate list is
+// short (the common case once clusters localize): one thread walks the
+// intersection serially — 64x fewer wave slots than the wave path. Same
+// core as the wave kernel, sim rows read from global memory (no LDS).
+__global__ void link_update_small_kernel(
+    const uint8_t* __restrict__ small_mask, int64_t n_recs,
+    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
+    const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
+    const int64_t* __restrict__ cand_lo, const int64_t* __restrict__ cand_hi,
+    const int32_t* __restrict__ postings, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ ent_ptr, const float* __restrict__ log_norm,
+    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
+    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
+    const uint8_t* __restrict__ attr_const, const int32_t* __restrict__ pair_a1,
+    const int32_t* __restrict__ pair_a2, int NP, int A, uint64_t seed,
+    uint32_t iteration, const int64_t* __restrict__ ctrl,
+    int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
+    int* __restrict__ error_count) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= n_recs || small_mask[r] != 1) return;
+  ctrl_override(ctrl, seed, iteration);
+
+  const auto [nd_mask, od_mask] =
+      link_classify(rec_values, rec_dist, attr_const, r, A);
+  const LinkBase base = link_select_base(cand_lo, cand_hi, pair_a1, pair_a2,
+                                         NP, rec_part, ent_ptr, r, A, nd_mask);
+  const auto sim = [&](int, int64_t row, int32_t y) {
+    return sim_lookup(csr_row_ptr, csr_col, csr_sim, row, y);
+  };
+  const uint64_t gid = (uint64_t)rec_gid[r];
+  float best_score = -INFINITY;
+  long long best_e = -1;
+  for (int64_t i = base.lo; i < base.lo + base.n; ++i) {
+    const int32_t e = base.postings ? postings[i] : (int32_t)i;
+    if (!link_matches(ent_values, rec_values, e, r, A, base.check_mask)) continue;
+    const float logw =
+        link_logw(ent_values, rec_values, log_norm, voff, e, r, A, od_mask, sim);
+    const float g = gumbel_from_uniform(
+        philox_uniform(seed, iteration, PH_LINK, gid, (uint32_t)e));
+    if (logw + g > best_score) { best_score = logw + g; best_e = e; }
   }
-  rec_ent_out[r] = best_e;
+  rec_ent_out[r] = link_winner_or_keep(best_e, rec_ent_in, r, error_count);
 }
 
 // ---------------------------------------------------------------------------
@@ -390,16 +419,11 @@ __global__ void link_update_heavy_kernel(
   __shared__ float simh_v_s[HEAVY_WAVES][SIMH_CAP];
   const int64_t r = (int64_t)blockIdx.x * HEAVY_WAVES + wid;
   if (r >= R || mode[r] != 2) return;
-  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
+  ctrl_override(ctrl, seed, iteration);
 
   const int T = A + NP;
-  uint32_t nd_mask = 0, od_mask = 0;
-  for (int a = 0; a < A; ++a) {
-    const int32_t x = rec_values[r * A + a];
-    if (x < 0) continue;
-    if (!rec_dist[r * A + a]) nd_mask |= 1u << a;
-    else if (!attr_const[a]) od_mask |= 1u << a;
-  }
+  const auto [nd_mask, od_mask] =
+      link_classify(rec_values, rec_dist, attr_const, r, A);
   const int32_t p = rec_part[r];
   const int64_t e0 = ent_ptr[p], e1 = ent_ptr[p + 1];
   const uint64_t gid = (uint64_t)rec_gid[r];
@@ -426,6 +450,10 @@ __global__ void link_update_heavy_kernel(
   if (simh_on && od_mask)
     simh_stage(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, od_mask, logpk, offpk);
+  const auto sim = [&](int a, int64_t row, int32_t y) {
+    return simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr, csr_col,
+                       csr_sim, row, y);
+  };
 
   // ---- 1. exact scan over the similar set S_r ----------------------------
   // The sim-row's posting segments average only a few entries, so a
@@ -474,27 +502,9 @@ __global__ void link_update_heavy_kernel(
         const float dsim = __shfl(simv, fl);  // sim of the enumerated attr
         if (s >= total) continue;
         const int32_t e = postings[i];
-        bool ok = true;
-        for (uint32_t mm = nd_mask; mm;) {
-          const int aa = __ffs(mm) - 1;
-          mm &= mm - 1;
-          if (ent_values[(int64_t)e * A + aa] != rec_values[r * A + aa]) {
-            ok = false;
-            break;
-          }
-        }
-        if (!ok) continue;
-        float logw = 0.0f;
-        for (uint32_t mo = od_mask; mo;) {
-          const int ao = __ffs(mo) - 1;
-          mo &= mo - 1;
-          const int32_t y = ent_values[(int64_t)e * A + ao];
-          logw += log_norm[voff[ao] + y] +
-                  (ao == a ? dsim
-                           : simh_lookup(simh_k, simh_v, logpk, offpk, ao,
-                                         csr_row_ptr, csr_col, csr_sim,
-                                         voff[ao] + rec_values[r * A + ao], y));
-        }
+        if (!link_matches(ent_values, rec_values, e, r, A, nd_mask)) continue;
+        const float logw = link_logw(ent_values, rec_values, log_norm, voff, e,
+                                     r, A, od_mask, sim, a, dsim);
         const float g = gumbel_from_uniform(
             philox_uniform(seed, iteration, PH_LINK, gid, (uint32_t)e));
         if (logw + g > best_f) { best_f = logw + g; best_e = e; }
@@ -557,25 +567,16 @@ __global__ void link_update_heavy_kernel(
       Z -= 1.0;
       ++iters;
       const int32_t e = seg_pool ? postings[plo + ci] : (int32_t)(plo + ci);
-      bool ok = true;
-      for (uint32_t mm = nd_mask; mm;) {
-        const int aa = __ffs(mm) - 1;
-        mm &= mm - 1;
-        if (ent_values[(int64_t)e * A + aa] != rec_values[r * A + aa]) {
-          ok = false;
-          break;
-        }
-      }
-      if (!ok) continue;
+      if (!link_matches(ent_values, rec_values, e, r, A, nd_mask)) continue;
+      // f64 log-weight with the tau early exit: not link_logw (that one is
+      // f32 and has no exit), and must stay in step with it by hand
       double t = 0.0;
       bool in_big = false;
       for (uint32_t mo = od_mask; mo;) {
         const int ao = __ffs(mo) - 1;
         mo &= mo - 1;
         const int32_t y = ent_values[(int64_t)e * A + ao];
-        const float s = simh_lookup(simh_k, simh_v, logpk, offpk, ao,
-                                    csr_row_ptr, csr_col, csr_sim,
-                                    voff[ao] + rec_values[r * A + ao], y);
+        const float s = sim(ao, voff[ao] + rec_values[r * A + ao], y);
         if (s >= tau) { in_big = true; break; }  // scored exactly in S_r
         t += (double)(log_norm[voff[ao] + y] + s);
       }
@@ -598,23 +599,9 @@ __global__ void link_update_heavy_kernel(
     float bf = -INFINITY;
     long long be = -1;
     for (int64_t e = e0 + lane; e < e1; e += WAVE) {
-      bool ok = true;
-      for (uint32_t mm = nd_mask; mm;) {
-        const int aa = __ffs(mm) - 1;
-        mm &= mm - 1;
-        if (ent_values[e * A + aa] != rec_values[r * A + aa]) { ok = false; break; }
-      }
-      if (!ok) continue;
-      float logw = 0.0f;
-      for (uint32_t mo = od_mask; mo;) {
-        const int ao = __ffs(mo) - 1;
-        mo &= mo - 1;
-        const int32_t y = ent_values[e * A + ao];
-        logw += log_norm[voff[ao] + y] +
-                simh_lookup(simh_k, simh_v, logpk, offpk, ao, csr_row_ptr,
-                            csr_col, csr_sim,
-                            voff[ao] + rec_values[r * A + ao], y);
-      }
+      if (!link_matches(ent_values, rec_values, e, r, A, nd_mask)) continue;
+      const float logw = link_logw(ent_values, rec_values, log_norm, voff, e,
+                                   r, A, od_mask, sim);
       const float g = gumbel_from_uniform(
           philox_uniform(seed, iteration, PH_LINKF, gid, (uint32_t)(e - e0)));
       if (logw + g > bf) { bf = logw + g; be = e; }
@@ -622,14 +609,9 @@ __global__ void link_update_heavy_kernel(
     wave_argmax(bf, be);
     if (lane == 0) winner_s[wid] = be;
   }
-  if (lane == 0) {
-    long long w = winner_s[wid];
-    if (w < 0) {  // empty candidate set: state invariant violated
-      atomicAdd(error_count, 1);
-      w = rec_ent_in[r];
-    }
-    rec_ent_out[r] = w;
-  }
+  if (lane == 0)
+    rec_ent_out[r] =
+        link_winner_or_keep(winner_s[wid], rec_ent_in, r, error_count);
 }
 
 // ---------------------------------------------------------------------------
@@ -656,7 +638,7 @@ __global__ void link_update_dense_kernel(
   __shared__ float simh_v_s[4][SIMH_CAP];
   const int64_t r = (int64_t)blockIdx.x * (blockDim.x / WAVE) + wid;
   if (r >= R) return;
-  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
+  ctrl_override(ctrl, seed, iteration);
   const int32_t p = rec_part[r];
   const int64_t e0 = ent_ptr[p], e1 = ent_ptr[p + 1];
   const int f = rec_file[r];
@@ -802,10 +784,7 @@ __device__ int dense_power_draw(const ValueArgs& args, int a, int k, uint64_t el
 // Thread-per-pair base draws for empty clusters (k_obs == 0): the base
 // distribution is phi for every variant (GibbsUpdates.scala:584-588).
 __global__ void value_base_draw_kernel(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= args.n_pairs) return;
   const int64_t pair = args.pair_list ? args.pair_list[i] : i;
@@ -829,10 +808,7 @@ __global__ void value_base_draw_kernel(ValueArgs args) {
 // row totals, a draw is: one Philox call, a mixture test, and one binary
 // search over the row prefix — O(log row) regardless of row size.
 __global__ void value_update_k1_kernel(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= args.n_pairs) return;
   const int64_t pair = args.pair_list ? args.pair_list[i] : i;
@@ -928,10 +904,7 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
 // self-power correction, a mixture test and one binary search — O(log row)
 // like the k = 1 kernel, replacing an O(k row) wave merge.
 __global__ void value_update_kd1_kernel(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= args.n_pairs) return;
   const int64_t pair = i;
@@ -1196,10 +1169,7 @@ __device__ void value_update_kd2_pair(const ValueArgs& args, int64_t pair,
 
 __global__ void __launch_bounds__(WAVES_PER_BLOCK_VAL * WAVE)
 value_update_kd2_kernel(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
   const int64_t widx = (int64_t)blockIdx.x * WAVES_PER_BLOCK_VAL + wave;
@@ -1223,10 +1193,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
 template <int VMODE>
 __global__ void __launch_bounds__(WAVES_PER_BLOCK_VAL * WAVE)
 value_update_kernel_t(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   __shared__ int32_t h_key[WAVES_PER_BLOCK_VAL][HASH_CAP];
   __shared__ float h_val[WAVES_PER_BLOCK_VAL][HASH_CAP];
   __shared__ int32_t g_buf[WAVES_PER_BLOCK_VAL][3 * VAL_DMAX + 1];
@@ -1748,10 +1715,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
 
 // Brute-force dense value update (Gibbs-Sequential, GibbsUpdates.scala:652-698)
 __global__ void value_update_seq_kernel(ValueArgs args) {
-  if (args.ctrl != nullptr) {
-    args.seed = (uint64_t)args.ctrl[0];
-    args.iteration = (uint32_t)args.ctrl[1];
-  }
+  ctrl_override(args.ctrl, args.seed, args.iteration);
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
   const int64_t pair = (int64_t)blockIdx.x * (blockDim.x / WAVE) + wave;
@@ -1827,7 +1791,7 @@ __global__ void distortion_update_kernel(
     int64_t E,                      // entity prior rows (0 when not fusing)
     double* __restrict__ loglik) {  // nullptr = distortion only
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (ctrl != nullptr) { seed = (uint64_t)ctrl[0]; iteration = (uint32_t)ctrl[1]; }
+  ctrl_override(ctrl, seed, iteration);
   double contrib = 0.0;
   if (idx < E * A) {
     const int64_t e = idx / A;
@@ -2467,6 +2431,61 @@ static int simh_enabled() {
   return e ? std::atoi(e) : 1;
 }
 
+// Operands common to the link launchers, checked and unpacked in one place.
+// The kernels keep flat __restrict__ parameters (struct members would lose
+// the qualifier and with it the scalar loads); this bundles the host side.
+// Shapes are on link_update_kernel's parameter list.
+struct LinkArgs {
+  const int32_t *rec_values, *rec_part, *ent_values, *csr_col;
+  const uint8_t *rec_dist, *attr_const;
+  const int64_t *rec_gid, *ent_ptr, *voff, *csr_row_ptr;
+  const int64_t* ctrl;          // {seed, iteration} device override (or null)
+  const float *log_norm, *csr_sim;
+  int64_t* rec_ent_out;
+  const int64_t* rec_ent_in;    // dense path: null, like log_norm, error_count
+  int* error_count;
+  int64_t R;
+  uint64_t seed;
+  uint32_t iteration;
+  int A, simh_on;
+};
+
+static LinkArgs make_link_args(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
+    torch::Tensor rec_part, torch::Tensor ent_values, torch::Tensor ent_ptr,
+    torch::Tensor log_norm, torch::Tensor voff, torch::Tensor csr_row_ptr,
+    torch::Tensor csr_col, torch::Tensor csr_sim, torch::Tensor attr_const,
+    int64_t seed, int64_t iteration, torch::Tensor ctrl,
+    torch::Tensor rec_ent_out, torch::Tensor rec_ent_in,
+    torch::Tensor error_count) {
+  CHECK_GPU(rec_values);
+  LinkArgs a;
+  a.R = rec_values.size(0);
+  a.A = (int)rec_values.size(1);
+  // 32-bit attr masks; nibble-packed staging descriptors hold 16 attributes
+  TORCH_CHECK(a.A <= MAX_ATTRS, "at most ", MAX_ATTRS, " matching attributes supported");
+  a.rec_values = rec_values.data_ptr<int32_t>();
+  a.rec_dist = rec_dist.data_ptr<uint8_t>();
+  a.rec_gid = rec_gid.data_ptr<int64_t>();
+  a.rec_part = rec_part.data_ptr<int32_t>();
+  a.ent_values = ent_values.data_ptr<int32_t>();
+  a.ent_ptr = ent_ptr.data_ptr<int64_t>();
+  a.log_norm = log_norm.defined() ? log_norm.data_ptr<float>() : nullptr;
+  a.voff = voff.data_ptr<int64_t>();
+  a.csr_row_ptr = csr_row_ptr.data_ptr<int64_t>();
+  a.csr_col = csr_col.data_ptr<int32_t>();
+  a.csr_sim = csr_sim.data_ptr<float>();
+  a.attr_const = attr_const.data_ptr<uint8_t>();
+  a.seed = (uint64_t)seed;
+  a.iteration = (uint32_t)iteration;
+  a.ctrl = ctrl.numel() ? ctrl.data_ptr<int64_t>() : nullptr;
+  a.rec_ent_out = rec_ent_out.data_ptr<int64_t>();
+  a.rec_ent_in = rec_ent_in.defined() ? rec_ent_in.data_ptr<int64_t>() : nullptr;
+  a.error_count = error_count.defined() ? error_count.data_ptr<int>() : nullptr;
+  a.simh_on = simh_enabled();
+  return a;
+}
+
 void link_update(
     torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
     torch::Tensor rec_part, torch::Tensor cand_lo, torch::Tensor cand_hi,
@@ -2477,53 +2496,36 @@ void link_update(
     torch::Tensor rec_ent_in, torch::Tensor error_count,
     torch::Tensor small_mask, torch::Tensor ctrl, torch::Tensor pair_a1,
     torch::Tensor pair_a2) {
-  const int64_t* ctrl_ptr = ctrl.numel() ? ctrl.data_ptr<int64_t>() : nullptr;
+  const LinkArgs L = make_link_args(
+      rec_values, rec_dist, rec_gid, rec_part, ent_values, ent_ptr, log_norm,
+      voff, csr_row_ptr, csr_col, csr_sim, attr_const, seed, iteration, ctrl,
+      rec_ent_out, rec_ent_in, error_count);
+  if (L.R == 0) return;
   const int NP = (int)pair_a1.numel();
-  CHECK_GPU(rec_values);
-  const int64_t R = rec_values.size(0);
-  const int A = (int)rec_values.size(1);
-  TORCH_CHECK(A <= MAX_ATTRS, "at most ", MAX_ATTRS, " matching attributes supported");
-  if (R == 0) return;
+  const int64_t* lo = cand_lo.data_ptr<int64_t>();
+  const int64_t* hi = cand_hi.data_ptr<int64_t>();
+  const int32_t* post = postings.data_ptr<int32_t>();
+  const int32_t* a1 = pair_a1.data_ptr<int32_t>();
+  const int32_t* a2 = pair_a2.data_ptr<int32_t>();
   constexpr int WPB = 4;
   const bool split = small_mask.numel() > 0;
   const uint8_t* mask_ptr = split ? small_mask.data_ptr<uint8_t>() : nullptr;
-  {
-    dim3 grid((unsigned)wave_grid(R, WPB));
-    hipLaunchKernelGGL(link_update_kernel, grid, dim3(WPB * WAVE), 0,
-                       at::cuda::getCurrentCUDAStream(),
-                       rec_values.data_ptr<int32_t>(), rec_dist.data_ptr<uint8_t>(),
-                       rec_gid.data_ptr<int64_t>(), rec_part.data_ptr<int32_t>(),
-                       cand_lo.data_ptr<int64_t>(), cand_hi.data_ptr<int64_t>(),
-                       postings.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
-                       ent_ptr.data_ptr<int64_t>(), log_norm.data_ptr<float>(),
-                       voff.data_ptr<int64_t>(), csr_row_ptr.data_ptr<int64_t>(),
-                       csr_col.data_ptr<int32_t>(), csr_sim.data_ptr<float>(),
-                       attr_const.data_ptr<uint8_t>(),
-                       pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
-                       NP, mask_ptr, R, A,
-                       (uint64_t)seed, (uint32_t)iteration, ctrl_ptr,
-                       rec_ent_out.data_ptr<int64_t>(),
-                       rec_ent_in.data_ptr<int64_t>(), error_count.data_ptr<int>(),
-                       simh_enabled());
-  }
-  if (split) {
-    dim3 grid((unsigned)((R + 255) / 256));
-    hipLaunchKernelGGL(link_update_small_kernel, grid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(),
-                       mask_ptr, R,
-                       rec_values.data_ptr<int32_t>(), rec_dist.data_ptr<uint8_t>(),
-                       rec_gid.data_ptr<int64_t>(), cand_lo.data_ptr<int64_t>(),
-                       cand_hi.data_ptr<int64_t>(), postings.data_ptr<int32_t>(),
-                       ent_values.data_ptr<int32_t>(), log_norm.data_ptr<float>(),
-                       voff.data_ptr<int64_t>(), csr_row_ptr.data_ptr<int64_t>(),
-                       csr_col.data_ptr<int32_t>(), csr_sim.data_ptr<float>(),
-                       attr_const.data_ptr<uint8_t>(),
-                       pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
-                       NP, A, (uint64_t)seed,
-                       (uint32_t)iteration, ctrl_ptr,
-                       rec_ent_out.data_ptr<int64_t>(),
-                       rec_ent_in.data_ptr<int64_t>(), error_count.data_ptr<int>());
-  }
+  hipLaunchKernelGGL(link_update_kernel, dim3((unsigned)wave_grid(L.R, WPB)),
+                     dim3(WPB * WAVE), 0, at::cuda::getCurrentCUDAStream(),
+                     L.rec_values, L.rec_dist, L.rec_gid, L.rec_part, lo, hi,
+                     post, L.ent_values, L.ent_ptr, L.log_norm, L.voff,
+                     L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, a1, a2,
+                     NP, mask_ptr, L.R, L.A, L.seed, L.iteration, L.ctrl,
+                     L.rec_ent_out, L.rec_ent_in, L.error_count, L.simh_on);
+  if (split)
+    hipLaunchKernelGGL(link_update_small_kernel,
+                       dim3((unsigned)((L.R + 255) / 256)), dim3(256), 0,
+                       at::cuda::getCurrentCUDAStream(), mask_ptr, L.R,
+                       L.rec_values, L.rec_dist, L.rec_gid, L.rec_part, lo, hi,
+                       post, L.ent_values, L.ent_ptr, L.log_norm, L.voff,
+                       L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, a1,
+                       a2, NP, L.A, L.seed, L.iteration, L.ctrl, L.rec_ent_out,
+                       L.rec_ent_in, L.error_count);
 }
 
 void postings_hist(torch::Tensor ent_part, torch::Tensor ent_values,
@@ -2656,30 +2658,26 @@ void link_update_heavy(
     int64_t Vmax, int64_t NP, int64_t seed, int64_t iteration, torch::Tensor ctrl,
     torch::Tensor rec_ent_out, torch::Tensor rec_ent_in,
     torch::Tensor error_count, torch::Tensor stats) {
-  const int64_t* ctrl_ptr = ctrl.numel() ? ctrl.data_ptr<int64_t>() : nullptr;
-  const int64_t R = rec_values.size(0);
-  const int A = (int)rec_values.size(1);
-  if (R == 0) return;
-  dim3 grid((unsigned)wave_grid(R, HEAVY_WAVES));
-  hipLaunchKernelGGL(link_update_heavy_kernel, grid, dim3(HEAVY_WAVES * WAVE), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     mode.data_ptr<uint8_t>(), rec_values.data_ptr<int32_t>(),
-                     rec_dist.data_ptr<uint8_t>(), rec_gid.data_ptr<int64_t>(),
-                     rec_part.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
-                     ent_ptr.data_ptr<int64_t>(), log_norm.data_ptr<float>(),
-                     voff.data_ptr<int64_t>(), csr_row_ptr.data_ptr<int64_t>(),
-                     csr_col.data_ptr<int32_t>(), csr_sim.data_ptr<float>(),
-                     attr_const.data_ptr<uint8_t>(),
+  const LinkArgs L = make_link_args(
+      rec_values, rec_dist, rec_gid, rec_part, ent_values, ent_ptr, log_norm,
+      voff, csr_row_ptr, csr_col, csr_sim, attr_const, seed, iteration, ctrl,
+      rec_ent_out, rec_ent_in, error_count);
+  if (L.R == 0) return;
+  hipLaunchKernelGGL(link_update_heavy_kernel,
+                     dim3((unsigned)wave_grid(L.R, HEAVY_WAVES)),
+                     dim3(HEAVY_WAVES * WAVE), 0, at::cuda::getCurrentCUDAStream(),
+                     mode.data_ptr<uint8_t>(), L.rec_values, L.rec_dist,
+                     L.rec_gid, L.rec_part, L.ent_values, L.ent_ptr, L.log_norm,
+                     L.voff, L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const,
                      csr_row_ptr_big.data_ptr<int64_t>(),
                      csr_col_big.data_ptr<int32_t>(), csr_sim_big.data_ptr<float>(),
                      (float)tau, postings.data_ptr<int32_t>(),
-                     idx_ptr.data_ptr<int64_t>(), Vmax, (int)NP, R, A,
-                     (uint64_t)seed, (uint32_t)iteration, ctrl_ptr,
-                     rec_ent_out.data_ptr<int64_t>(), rec_ent_in.data_ptr<int64_t>(),
-                     error_count.data_ptr<int>(),
+                     idx_ptr.data_ptr<int64_t>(), Vmax, (int)NP, L.R, L.A,
+                     L.seed, L.iteration, L.ctrl, L.rec_ent_out, L.rec_ent_in,
+                     L.error_count,
                      stats.numel() ? (unsigned long long*)stats.data_ptr<int64_t>()
                                    : nullptr,
-                     simh_enabled());
+                     L.simh_on);
 }
 
 void cand_ranges(torch::Tensor rec_part, torch::Tensor rec_values,
@@ -2709,25 +2707,23 @@ void link_update_dense(
     torch::Tensor csr_col, torch::Tensor csr_sim, torch::Tensor attr_const,
     int64_t collapsed, int64_t seed, int64_t iteration, torch::Tensor rec_ent_out,
     torch::Tensor ctrl) {
-  const int64_t* ctrl_ptr = ctrl.numel() ? ctrl.data_ptr<int64_t>() : nullptr;
-  const int64_t R = rec_values.size(0);
-  const int A = (int)rec_values.size(1);
+  // linear norm_lin instead of log_norm; no empty-set tail (weights > 0)
+  const LinkArgs L = make_link_args(
+      rec_values, rec_dist, rec_gid, rec_part, ent_values, ent_ptr, {}, voff,
+      csr_row_ptr, csr_col, csr_sim, attr_const, seed, iteration, ctrl,
+      rec_ent_out, {}, {});
   const int F = (int)theta.size(1);
-  if (R == 0) return;
+  if (L.R == 0) return;
   constexpr int WPB = 4;
-  dim3 grid((unsigned)wave_grid(R, WPB));
-  hipLaunchKernelGGL(link_update_dense_kernel, grid, dim3(WPB * WAVE), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     rec_values.data_ptr<int32_t>(), rec_dist.data_ptr<uint8_t>(),
-                     rec_gid.data_ptr<int64_t>(), rec_part.data_ptr<int32_t>(),
-                     rec_file.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
-                     ent_ptr.data_ptr<int64_t>(), theta.data_ptr<float>(),
-                     phi.data_ptr<float>(), norm_lin.data_ptr<float>(),
-                     voff.data_ptr<int64_t>(), csr_row_ptr.data_ptr<int64_t>(),
-                     csr_col.data_ptr<int32_t>(), csr_sim.data_ptr<float>(),
-                     attr_const.data_ptr<uint8_t>(), R, A, F, (int)collapsed,
-                     (uint64_t)seed, (uint32_t)iteration, ctrl_ptr,
-                     rec_ent_out.data_ptr<int64_t>(), simh_enabled());
+  hipLaunchKernelGGL(link_update_dense_kernel,
+                     dim3((unsigned)wave_grid(L.R, WPB)), dim3(WPB * WAVE), 0,
+                     at::cuda::getCurrentCUDAStream(), L.rec_values, L.rec_dist,
+                     L.rec_gid, L.rec_part, rec_file.data_ptr<int32_t>(),
+                     L.ent_values, L.ent_ptr, theta.data_ptr<float>(),
+                     phi.data_ptr<float>(), norm_lin.data_ptr<float>(), L.voff,
+                     L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, L.R, L.A,
+                     F, (int)collapsed, L.seed, L.iteration, L.ctrl,
+                     L.rec_ent_out, L.simh_on);
 }
 
 // Opt-in value-phase work counters (DBLink_VALUE_STATS): set once from

@@ -832,6 +832,106 @@ def test_link_kernel_parity_on_realistic_state():
         )
 
 
+def _link_paths_inputs(n_vals, seed=3, E=600, R=512):
+    """Pure-numpy inputs for the wave/thread agreement test: E entities in one
+    partition, R records copied from random entities and perturbed into five
+    kinds (attr 0 = constant 'year', attr 1 = Levenshtein 'name'):
+      0 year non-distorted, name distorted     (the only kind with an od attr)
+      1 name non-distorted, year distorted
+      2 both non-distorted
+      3 year missing, name non-distorted
+      4 name missing, year non-distorted
+    Kind 0 takes 6 records in 10 so most records score a real od log-weight.
+    Returns the arrays plus, per record, the number of entities passing the
+    equality checks and whether od_mask is non-empty."""
+    rng = np.random.default_rng(seed)
+    A = len(n_vals)
+    Vmax = max(n_vals)
+    ent_values = np.stack([rng.integers(0, v, size=E) for v in n_vals], 1).astype(np.int32)
+    kind = np.array([0, 0, 0, 0, 0, 0, 1, 2, 3, 4])[np.arange(R) % 10]
+    rec_values = ent_values[rng.integers(0, E, size=R)].copy()
+    rec_dist = np.zeros((R, A), dtype=np.uint8)
+    k0, k1 = kind == 0, kind == 1
+    rec_dist[k0, 1] = 1
+    rec_values[k0, 1] = rng.integers(0, n_vals[1], size=k0.sum())
+    rec_dist[k1, 0] = 1
+    rec_values[k1, 0] = rng.integers(0, n_vals[0], size=k1.sum())
+    rec_values[kind == 3, 0] = -1
+    rec_values[kind == 4, 1] = -1
+
+    # posting build identical to the engine (slot-major keys, one partition)
+    keys = (np.repeat(np.arange(A), E) * Vmax + ent_values.T.reshape(-1)).astype(np.int64)
+    order = np.argsort(keys, kind="stable")
+    postings = (order % E).astype(np.int32)
+    qk = np.arange(A)[None, :] * Vmax + np.maximum(rec_values, 0)
+    cand_lo = np.searchsorted(keys[order], qk, "left")
+    cand_hi = np.searchsorted(keys[order], qk, "right")
+
+    nd = (rec_values >= 0) & (rec_dist == 0)
+    match = ((ent_values[None] == rec_values[:, None]) | ~nd[:, None]).all(2)
+    has_od = (rec_values[:, 1] >= 0) & (rec_dist[:, 1] == 1)  # attr 0 is constant
+    return dict(ent_values=ent_values, rec_values=rec_values, rec_dist=rec_dist,
+                kind=kind, postings=postings, cand_lo=cand_lo, cand_hi=cand_hi,
+                nd=nd, n_match=match.sum(1), has_od=has_od)
+
+
+@gpu
+def test_link_wave_and_thread_paths_agree_bitwise(monkeypatch):
+    """Routing a record to the wave or the thread link kernel is a performance
+    decision, and LDS sim-row staging is an optimisation: all three must draw
+    the SAME entity for every record. Identical inputs, seed and iteration
+    through (a) the wave path, (b) the thread path, (c) the wave path with
+    staging off; outputs must be torch.equal. Year postings hold ~60 entities,
+    so staging engages in (a); every record has an observed non-distorted
+    attribute, as the thread kernel's routing guarantees."""
+    cache, model = make_model(DEV)
+    n_vals = [ia.index.num_values for ia in cache.indexed_attributes]
+    d = _link_paths_inputs(n_vals)
+    E, R = d["ent_values"].shape[0], d["rec_values"].shape[0]
+
+    # the check must not be vacuous
+    assert d["nd"].any(1).all()
+    assert (d["n_match"] >= 1).all()
+    assert ((d["n_match"] >= 2) & d["has_od"]).sum() >= R // 2
+    assert set(d["kind"].tolist()) == {0, 1, 2, 3, 4}
+    year_nd = d["nd"][:, 0]
+    assert ((d["cand_hi"] - d["cand_lo"])[year_nd, 0] >= 32).all()
+
+    args_head = (
+        _dev(d["rec_values"], torch.int32), _dev(d["rec_dist"], torch.uint8),
+        _dev(np.arange(R, dtype=np.int64), torch.int64),
+        _dev(np.zeros(R, np.int32), torch.int32),
+        _dev(d["cand_lo"], torch.int64), _dev(d["cand_hi"], torch.int64),
+        _dev(d["postings"], torch.int32), _dev(d["ent_values"], torch.int32),
+        _dev(np.array([0, E], dtype=np.int64), torch.int64),
+        model.log_norm, model.voff, model.csr_row_ptr, model.csr_col,
+        model.csr_sim, model.attr_const, 4242, 7,
+    )
+    rec_ent_in = _dev(np.zeros(R, np.int64), torch.int64)
+    no_pairs = torch.empty(0, dtype=torch.int32, device=DEV)
+
+    def run(small_mask):
+        out = torch.full((R,), -7, dtype=torch.int64, device=DEV)
+        err = torch.zeros(1, dtype=torch.int32, device=DEV)
+        C.link_update(*args_head, out, rec_ent_in, err, small_mask,
+                      torch.empty(0, dtype=torch.int64, device=DEV),
+                      no_pairs, no_pairs)
+        assert int(err.cpu()) == 0
+        return out
+
+    wave = run(torch.empty(0, dtype=torch.uint8, device=DEV))
+    thread = run(torch.ones(R, dtype=torch.uint8, device=DEV))
+    monkeypatch.setenv("DBLINK_SIMH", "0")  # re-read per launch; restored on exit
+    wave_global = run(torch.empty(0, dtype=torch.uint8, device=DEV))
+
+    assert torch.equal(wave, thread)
+    assert torch.equal(wave, wave_global)
+    sel = wave.cpu().numpy()
+    assert (sel >= 0).all() and (sel < E).all()
+    # every draw is a legal candidate (equal on all non-distorted attrs)
+    assert ((d["ent_values"][sel] == d["rec_values"]) | ~d["nd"]).all()
+
+
 @gpu
 def test_link_heavy_kernel_distribution():
     """Hierarchical A* link sampler (link_update_heavy_kernel) vs exact
