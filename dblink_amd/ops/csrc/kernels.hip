@@ -760,6 +760,141 @@ struct ValueArgs {
   int vchunk;  // 1 = chunked hash-accumulate dense path (DBLINK_VCHUNK)
 };
 
+// --- shared draw core --------------------------------------------------------
+// Every value kernel below is built from these pieces. Which kernel (and
+// which k >= 2 path inside it) handles a pair is a performance decision; the
+// distribution drawn from must not depend on it, so the pieces exist once.
+
+struct ValuePair {
+  int64_t e;
+  int a;
+  int64_t v0;     // attribute a's offset into the value-indexed tables
+  int V;          // attribute a's domain size
+  uint64_t elem;  // Philox element id of the pair
+  bool is_const;
+};
+
+DBL_D ValuePair value_pair_of(const ValueArgs& args, int64_t pair) {
+  const int64_t e = pair / args.A;
+  const int a = (int)(pair % args.A);
+  const bool is_const = args.attr_const[a];
+  const int64_t v0 = args.voff[a];
+  const int V = (int)(args.voff[a + 1] - v0);
+  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
+  return {e, a, v0, V, elem, is_const};
+}
+
+// The table kernels' four uniforms: mixture test, CDF target (both f64: the
+// prefix tables are f64) and the two alias-draw uniforms.
+struct ValueUniforms { double u_mix, u_sel; float u_a1, u_a2; };
+
+DBL_D ValueUniforms value_uniforms(const ValueArgs& args, uint64_t elem) {
+  const u32x4 rnd = philox4x32(args.seed, (uint32_t)elem, (uint32_t)(elem >> 32),
+                               args.iteration ^ (PH_VALM << 24), 0xFFFF0000u);
+  return {((double)rnd.x + 0.5) * 2.3283064365386963e-10,
+          ((double)rnd.y + 0.5) * 2.3283064365386963e-10,
+          u32_to_uniform(rnd.z), u32_to_uniform(rnd.w)};
+}
+
+// Value at the last row entry whose exclusive prefix is <= t: first entry
+// whose prefix exceeds t, minus one, clamped to the row.
+DBL_D int32_t prefix_pick(const double* excl, const int32_t* col, int64_t row_lo,
+                          int64_t row_hi, double t) {
+  int64_t lo = row_lo, hi = row_hi;
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (excl[mid] <= t) lo = mid + 1; else hi = mid;
+  }
+  int64_t jidx = lo - 1;
+  if (jidx < row_lo) jidx = row_lo;
+  if (jidx >= row_hi) jidx = row_hi - 1;
+  return col[jidx];
+}
+
+// Base draw from a cached alias table: phi for const attributes or k == 0
+// (GibbsUpdates.scala:584-588), else the power distribution phi norm^k
+// (1 <= k <= Kc).
+DBL_D int value_base_alias(const ValueArgs& args, const ValuePair& p, int k,
+                           float u1, float u2) {
+  if (p.is_const || k == 0)
+    return alias_draw(args.phi_prob + p.v0, args.phi_alias + p.v0, p.V, u1, u2);
+  const int64_t off = args.pow_off[p.a] + (int64_t)(k - 1) * p.V;
+  return alias_draw(args.pow_prob + off, args.pow_alias + off, p.V, u1, u2);
+}
+
+// Collapsed self term of a record with value x from file f: phi*norm*se
+// collapses to (1/theta - 1). The wave paths work in f32 and the table
+// kernels in f64; the two are not interchangeable bit for bit.
+DBL_D float value_self_f32(const ValueArgs& args, const ValuePair& p, int32_t x,
+                           int32_t f) {
+  if (!args.collapsed) return 0.0f;
+  const float th = args.theta[p.a * args.F + f];
+  const float px = args.phi[p.v0 + x];
+  return (1.0f / th - 1.0f) / (p.is_const ? px : px * args.norm_lin[p.v0 + x]);
+}
+
+DBL_D double value_self_f64(const ValueArgs& args, const ValuePair& p, int32_t x,
+                            int32_t f) {
+  if (!args.collapsed) return 0.0;
+  const double th = (double)args.theta[p.a * args.F + f];
+  return (1.0 / th - 1.0) /
+         ((double)args.phi[p.v0 + x] * (double)args.norm_lin[p.v0 + x]);
+}
+
+// Per-wave LDS open-addressing table (mask = size - 1): vals[slot of v] += x.
+DBL_D void lds_hash_add(int32_t* keys, float* vals, uint32_t mask, int32_t v,
+                        float x) {
+  uint32_t h = ((uint32_t)v * 2654435761u) & mask;
+  while (true) {
+    const int32_t prev = atomicCAS(&keys[h], -1, v);
+    if (prev == -1 || prev == v) { atomicAdd(&vals[h], x); break; }
+    h = (h + 1) & mask;
+  }
+}
+
+DBL_D void lds_hash_clear(int32_t* keys, float* vals, int size, int lane) {
+  for (int i = lane; i < size; i += WAVE) { keys[i] = -1; vals[i] = 0.0f; }
+  // drain LDS writes before other lanes' atomics may touch the slots
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+}
+
+// Log factor one row entry (value v, log-sim s) of a unit (value ux,
+// multiplicity fm) contributes: the self point carries the self term.
+DBL_D float row_factor_log(int32_t v, int32_t ux, float s, float fm,
+                           float self_extra) {
+  return (v == ux && self_extra > 0.0f) ? fm * __logf(__expf(s) + self_extra)
+                                        : fm * s;
+}
+
+// One support value with summed log factor L > 0 and log base probability
+// log_base: weight base * (e^L - 1) into W, keyed Gumbel into the running
+// best. log(exp(L) - 1) = L + log1p(-exp(-L)), stable for L > 0.
+DBL_D void value_accum(const ValueArgs& args, uint64_t elem, int32_t v, float L,
+                       float log_base, double& W, float& best, long long& best_v) {
+  const float log_expm1 = L + __logf(1.0f - __expf(-L));
+  const float logw = log_base + log_expm1;
+  W += (logw < 80.0f) ? (double)__expf(logw) : exp((double)logw);
+  const float g = gumbel_from_uniform(
+      philox_uniform(args.seed, args.iteration, PH_VALG, elem, (uint32_t)v));
+  if (logw + g > best) { best = logw + g; best_v = v; }
+}
+
+// Drain the table's atomics, then value_accum every occupied slot.
+template <class LogBase>
+DBL_D void lds_hash_reduce(const ValueArgs& args, uint64_t elem,
+                           const int32_t* keys, const float* vals, int size,
+                           int lane, const LogBase& log_base, double& W,
+                           float& best, long long& best_v) {
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  for (int i = lane; i < size; i += WAVE) {
+    const int32_t v = keys[i];
+    if (v < 0) continue;
+    value_accum(args, elem, v, vals[i], log_base(v), W, best, best_v);
+  }
+}
+
 // Draw from p(v) ~ phi(v)*norm(v)^k by a dense Gumbel scan (rare path for
 // k > Kc where no alias table is cached). Also returns log Z_k via wave sum.
 __device__ int dense_power_draw(const ValueArgs& args, int a, int k, uint64_t elem,
@@ -789,15 +924,10 @@ __global__ void value_base_draw_kernel(ValueArgs args) {
   if (i >= args.n_pairs) return;
   const int64_t pair = args.pair_list ? args.pair_list[i] : i;
   if (args.kobs && args.kobs[pair] != 0) return;
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
+  const ValuePair p = value_pair_of(args, pair);
   float u1, u2;
-  philox_uniform2(args.seed, args.iteration, PH_VALM, elem, 0xFFFF0000u, &u1, &u2);
-  const int v = alias_draw(args.phi_prob + v0, args.phi_alias + v0, V, u1, u2);
-  args.ent_values[e * args.A + a] = (int32_t)v;
+  philox_uniform2(args.seed, args.iteration, PH_VALM, p.elem, 0xFFFF0000u, &u1, &u2);
+  args.ent_values[p.e * args.A + p.a] = (int32_t)value_base_alias(args, p, 0, u1, u2);
 }
 
 // Thread-per-pair value update for single-record clusters (k_obs == 1).
@@ -813,12 +943,10 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
   if (i >= args.n_pairs) return;
   const int64_t pair = args.pair_list ? args.pair_list[i] : i;
   if (args.kobs && args.kobs[pair] != 1) return;
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  const bool is_const = args.attr_const[a];
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
+  const ValuePair p = value_pair_of(args, pair);
+  const int64_t e = p.e, v0 = p.v0;
+  const int a = p.a;
+  const bool is_const = p.is_const;
 
   // locate the single observed linked record
   const int64_t r_lo = args.ent_rec_ptr[e], r_hi = args.ent_rec_ptr[e + 1];
@@ -836,18 +964,9 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
     return;
   }
 
-  u32x4 rnd = philox4x32(args.seed, (uint32_t)elem, (uint32_t)(elem >> 32),
-                         args.iteration ^ (PH_VALM << 24), 0xFFFF0000u);
-  const double u_mix = ((double)rnd.x + 0.5) * 2.3283064365386963e-10;
-  const double u_sel = ((double)rnd.y + 0.5) * 2.3283064365386963e-10;
-  const float u_a1 = u32_to_uniform(rnd.z);
-  const float u_a2 = u32_to_uniform(rnd.w);
-
+  const ValueUniforms u = value_uniforms(args, p.elem);
   auto base_draw = [&]() -> int {
-    if (is_const)
-      return alias_draw(args.phi_prob + v0, args.phi_alias + v0, V, u_a1, u_a2);
-    const int64_t off = args.pow_off[a];  // k = 1 table
-    return alias_draw(args.pow_prob + off, args.pow_alias + off, V, u_a1, u_a2);
+    return value_base_alias(args, p, 1, u.u_a1, u.u_a2);
   };
   if (!args.collapsed && is_const) {
     args.ent_values[e * args.A + a] = (int32_t)base_draw();
@@ -871,27 +990,17 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
   }
 
   int v_new;
-  if (u_mix < 1.0 / (1.0 + Wnorm) || raw_total <= 0.0) {
+  if (u.u_mix < 1.0 / (1.0 + Wnorm) || raw_total <= 0.0) {
     v_new = base_draw();
   } else if (is_const) {
     v_new = x;  // the only support value
   } else {
-    const double t = u_sel * raw_total;
-    const int64_t row_lo = args.csr_row_ptr[v0 + x], row_hi = args.csr_row_ptr[v0 + x + 1];
-    if (t >= args.csr_rawsum[v0 + x]) {
+    const double t = u.u_sel * raw_total;
+    if (t >= args.csr_rawsum[v0 + x])
       v_new = x;  // self-correction mass
-    } else {
-      // first entry whose exclusive prefix exceeds t, minus one
-      int64_t lo = row_lo, hi = row_hi;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (args.csr_excl[mid] <= t) lo = mid + 1; else hi = mid;
-      }
-      int64_t jidx = lo - 1;
-      if (jidx < row_lo) jidx = row_lo;
-      if (jidx >= row_hi) jidx = row_hi - 1;
-      v_new = args.csr_col[jidx];
-    }
+    else
+      v_new = prefix_pick(args.csr_excl, args.csr_col, args.csr_row_ptr[v0 + x],
+                          args.csr_row_ptr[v0 + x + 1], t);
   }
   args.ent_values[e * args.A + a] = (int32_t)v_new;
 }
@@ -910,11 +1019,10 @@ __global__ void value_update_kd1_kernel(ValueArgs args) {
   const int64_t pair = i;
   const int k = args.kobs[pair];
   if (k < 2 || k > args.ktab_max) return;
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  if (args.attr_const[a]) return;
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
+  const ValuePair p = value_pair_of(args, pair);
+  if (p.is_const) return;
+  const int64_t e = p.e, v0 = p.v0;
+  const int a = p.a;
 
   // all observed linked records must share one (value, file); any
   // non-distorted observed record (non-collapsed) defers to the wave path
@@ -932,22 +1040,14 @@ __global__ void value_update_kd1_kernel(ValueArgs args) {
   if (x < 0) return;
   if (k > args.Kc) return;  // no cached power dist (rare path stays on wave)
 
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
-  u32x4 rnd = philox4x32(args.seed, (uint32_t)elem, (uint32_t)(elem >> 32),
-                         args.iteration ^ (PH_VALM << 24), 0xFFFF0000u);
-  const double u_mix = ((double)rnd.x + 0.5) * 2.3283064365386963e-10;
-  const double u_sel = ((double)rnd.y + 0.5) * 2.3283064365386963e-10;
-  const float u_a1 = u32_to_uniform(rnd.z);
-  const float u_a2 = u32_to_uniform(rnd.w);
+  const ValueUniforms u = value_uniforms(args, p.elem);
 
   const int lvl = k - 2;
   // theta-dependent self correction: the table carries the plain self
   // factor e^{k s(x,x)}; collapsed adds ((e^s + se)^k - e^{ks}) phi norm^k
   double extra = 0.0;
   if (args.collapsed) {
-    const double th = (double)args.theta[a * args.F + f];
-    const double phn = (double)args.phi[v0 + x] * (double)args.norm_lin[v0 + x];
-    const double se = (1.0 / th - 1.0) / phn;
+    const double se = value_self_f64(args, p, x, f);
     const double es = (double)args.self_expsim[v0 + x];
     double plain = 1.0, boosted = 1.0;
     for (int t = 0; t < k; ++t) { plain *= es; boosted *= es + se; }
@@ -960,27 +1060,15 @@ __global__ void value_update_kd1_kernel(ValueArgs args) {
   const double W = raw_total / Zk;
 
   int v_new;
-  if (u_mix < 1.0 / (1.0 + W) || raw_total <= 0.0) {
-    const int64_t off = args.pow_off[a] + (int64_t)(k - 1) * V;
-    v_new = alias_draw(args.pow_prob + off, args.pow_alias + off, V, u_a1, u_a2);
+  if (u.u_mix < 1.0 / (1.0 + W) || raw_total <= 0.0) {
+    v_new = value_base_alias(args, p, k, u.u_a1, u.u_a2);
   } else {
-    const double t = u_sel * raw_total;
-    if (t >= row_total) {
+    const double t = u.u_sel * raw_total;
+    if (t >= row_total)
       v_new = x;  // the self-correction mass
-    } else {
-      const int64_t row_lo = args.csr_row_ptr[v0 + x];
-      const int64_t row_hi = args.csr_row_ptr[v0 + x + 1];
-      const double* ex = args.tab_excl + (int64_t)lvl * args.nnz;
-      int64_t lo = row_lo, hi = row_hi;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ex[mid] <= t) lo = mid + 1; else hi = mid;
-      }
-      int64_t jidx = lo - 1;
-      if (jidx < row_lo) jidx = row_lo;
-      if (jidx >= row_hi) jidx = row_hi - 1;
-      v_new = args.csr_col[jidx];
-    }
+    else
+      v_new = prefix_pick(args.tab_excl + (int64_t)lvl * args.nnz, args.csr_col,
+                          args.csr_row_ptr[v0 + x], args.csr_row_ptr[v0 + x + 1], t);
   }
   args.ent_values[e * args.A + a] = (int32_t)v_new;
 }
@@ -1002,11 +1090,10 @@ __device__ void value_update_kd2_pair(const ValueArgs& args, int64_t pair,
                                       int lane) {
   const int k = args.kobs[pair];
   if (k < 2 || k > args.k2tab_max) return;
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  if (args.attr_const[a]) return;
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
+  const ValuePair p = value_pair_of(args, pair);
+  if (p.is_const) return;
+  const int64_t e = p.e, v0 = p.v0;
+  const int a = p.a;
   const int64_t Vtot = args.voff[args.A];
 
   // exactly two first-seen (value, file) groups with DISTINCT values
@@ -1034,13 +1121,8 @@ __device__ void value_update_kd2_pair(const ValueArgs& args, int64_t pair,
     return exp((double)args.log_phi[v0 + v] +
                (double)k * (double)args.log_norm[v0 + v]);
   };
-  auto se_at = [&](int32_t x, int f) -> double {
-    if (!args.collapsed) return 0.0;
-    const double th = (double)args.theta[a * args.F + f];
-    return (1.0 / th - 1.0) /
-           ((double)args.phi[v0 + x] * (double)args.norm_lin[v0 + x]);
-  };
-  const double se1 = se_at(x1, f1), se2 = se_at(x2, f2);
+  const double se1 = value_self_f64(args, p, x1, f1);
+  const double se2 = value_self_f64(args, p, x2, f2);
 
   auto resid_self = [&](int32_t xs, double ses, int ms, int32_t xo,
                         int mo) -> double {
@@ -1121,43 +1203,19 @@ __device__ void value_update_kd2_pair(const ValueArgs& args, int64_t pair,
   const double Zk = exp((double)args.log_pow_total[a * (args.Kc + 1) + k]);
   const double Wn = W / Zk;
 
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
-  u32x4 rnd = philox4x32(args.seed, (uint32_t)elem, (uint32_t)(elem >> 32),
-                         args.iteration ^ (PH_VALM << 24), 0xFFFF0000u);
-  const double u_mix = ((double)rnd.x + 0.5) * 2.3283064365386963e-10;
-  const double u_sel = ((double)rnd.y + 0.5) * 2.3283064365386963e-10;
-  const float u_a1 = u32_to_uniform(rnd.z);
-  const float u_a2 = u32_to_uniform(rnd.w);
+  const ValueUniforms u = value_uniforms(args, p.elem);
 
   int v_new;
-  if (u_mix < 1.0 / (1.0 + Wn) || W <= 0.0) {
-    const int64_t off = args.pow_off[a] + (int64_t)(k - 1) * V;
-    v_new = alias_draw(args.pow_prob + off, args.pow_alias + off, V, u_a1, u_a2);
+  if (u.u_mix < 1.0 / (1.0 + Wn) || W <= 0.0) {
+    v_new = value_base_alias(args, p, k, u.u_a1, u.u_a2);
   } else {
-    double t = u_sel * W;
+    const double t = u.u_sel * W;
     if (t < T1) {
-      const double* ex = args.tab2_excl + (int64_t)(lb + m1) * args.nnz;
-      int64_t lo = lo1, hi = hi1;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ex[mid] <= t) lo = mid + 1; else hi = mid;
-      }
-      int64_t jidx = lo - 1;
-      if (jidx < lo1) jidx = lo1;
-      if (jidx >= hi1) jidx = hi1 - 1;
-      v_new = args.csr_col[jidx];
+      v_new = prefix_pick(args.tab2_excl + (int64_t)(lb + m1) * args.nnz,
+                          args.csr_col, lo1, hi1, t);
     } else if (t < T1 + T2) {
-      t -= T1;
-      const double* ex = args.tab2_excl + (int64_t)(lb + m2) * args.nnz;
-      int64_t lo = lo2, hi = hi2;
-      while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (ex[mid] <= t) lo = mid + 1; else hi = mid;
-      }
-      int64_t jidx = lo - 1;
-      if (jidx < lo2) jidx = lo2;
-      if (jidx >= hi2) jidx = hi2 - 1;
-      v_new = args.csr_col[jidx];
+      v_new = prefix_pick(args.tab2_excl + (int64_t)(lb + m2) * args.nnz,
+                          args.csr_col, lo2, hi2, t - T1);
     } else {
       int32_t sel = x1;
       residual_pass(t - T1 - T2, &sel);
@@ -1181,6 +1239,10 @@ value_update_kd2_kernel(ValueArgs args) {
 
 constexpr int VAL_STRIDE = 8;  // pairs examined per wave in kobs mode
 
+// One factor of a pair's perturbation: a distinct (value, file) group of
+// observed records with its multiplicity, or a single record.
+struct ValueUnit { int32_t x, m, f; };
+
 // VMODE selects which k >= 2 perturbation path a kernel instantiation
 // carries: 0 = both (explicit pair lists / tests), 1 = LDS-hash only,
 // 2 = union-merge only. The split halves the register pressure of the hot
@@ -1188,50 +1250,12 @@ constexpr int VAL_STRIDE = 8;  // pairs examined per wave in kobs mode
 template <int VMODE>
 __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
                                   int32_t* keys, float* vals, int32_t* gbuf,
-                                  int64_t* glo, int32_t* gn, float* gse);
-
-template <int VMODE>
-__global__ void __launch_bounds__(WAVES_PER_BLOCK_VAL * WAVE)
-value_update_kernel_t(ValueArgs args) {
-  ctrl_override(args.ctrl, args.seed, args.iteration);
-  __shared__ int32_t h_key[WAVES_PER_BLOCK_VAL][HASH_CAP];
-  __shared__ float h_val[WAVES_PER_BLOCK_VAL][HASH_CAP];
-  __shared__ int32_t g_buf[WAVES_PER_BLOCK_VAL][3 * VAL_DMAX + 1];
-  // merge-path per-unit hoists: (row_lo, row_len, se) per distinct group
-  __shared__ int64_t g_lo[WAVES_PER_BLOCK_VAL][VAL_DMAX];
-  __shared__ int32_t g_n[WAVES_PER_BLOCK_VAL][VAL_DMAX];
-  __shared__ float g_se[WAVES_PER_BLOCK_VAL][VAL_DMAX];
-
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wave = threadIdx.x / WAVE;
-  const int64_t widx = (int64_t)blockIdx.x * WAVES_PER_BLOCK_VAL + wave;
-  if (args.pair_list != nullptr) {
-    if (widx >= args.n_pairs) return;
-    value_update_pair<VMODE>(args, args.pair_list[widx], lane, h_key[wave],
-                             h_val[wave], g_buf[wave], g_lo[wave], g_n[wave],
-                             g_se[wave]);
-  } else {
-    // kobs self-selection: each wave examines VAL_STRIDE consecutive pairs
-    // and runs the (rare) k >= 2 ones serially
-    const int64_t p0 = widx * VAL_STRIDE;
-    for (int64_t pair = p0; pair < p0 + VAL_STRIDE && pair < args.n_pairs; ++pair) {
-      if (args.kobs[pair] >= 2)
-        value_update_pair<VMODE>(args, pair, lane, h_key[wave], h_val[wave],
-                                 g_buf[wave], g_lo[wave], g_n[wave], g_se[wave]);
-    }
-  }
-}
-
-template <int VMODE>
-__device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
-                                  int32_t* keys, float* vals, int32_t* gbuf,
                                   int64_t* glo, int32_t* gn, float* gse) {
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  const bool is_const = args.attr_const[a];
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
+  const ValuePair p = value_pair_of(args, pair);
+  const int64_t e = p.e, v0 = p.v0;
+  const int a = p.a, V = p.V;
+  const bool is_const = p.is_const;
+  const uint64_t elem = p.elem;
 
   // ---- gather observed linked records -------------------------------------
   const int64_t r_lo = args.ent_rec_ptr[e], r_hi = args.ent_rec_ptr[e + 1];
@@ -1248,17 +1272,12 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
       first_nondist = x;
   }
 
-  // base distribution: phi for const attrs or k_obs == 0, else power dist k
+  // base distribution: cached alias tables, or the dense scan for k_obs > Kc
   auto base_draw = [&](uint32_t draw_tag) -> int {
     float u1, u2;
     philox_uniform2(args.seed, args.iteration, PH_VALM, elem, draw_tag, &u1, &u2);
-    if (is_const || k_obs == 0) {
-      return alias_draw(args.phi_prob + v0, args.phi_alias + v0, V, u1, u2);
-    }
-    if (k_obs <= args.Kc) {
-      const int64_t off = args.pow_off[a] + (int64_t)(k_obs - 1) * V;
-      return alias_draw(args.pow_prob + off, args.pow_alias + off, V, u1, u2);
-    }
+    if (is_const || k_obs == 0 || k_obs <= args.Kc)
+      return value_base_alias(args, p, k_obs, u1, u2);
     float dummy;
     return dense_power_draw(args, a, k_obs, elem, lane, &dummy);
   };
@@ -1299,12 +1318,6 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
     if (is_const) return args.log_phi[v];
     return args.log_phi[v] + (float)k_obs * args.log_norm[v] - log_z;
   };
-  auto self_extra_of = [&](int64_t r, int32_t x) -> float {
-    if (!args.collapsed) return 0.0f;
-    const float th = args.theta[a * args.F + args.rec_file[r]];
-    const float px = args.phi[v0 + x];
-    return (1.0f / th - 1.0f) / (is_const ? px : px * args.norm_lin[v0 + x]);
-  };
   auto finish = [&](double W, float best, long long best_v) {
     const float u = philox_uniform(args.seed, args.iteration, PH_VALM, elem, 0xFFFF0001u);
     int v_new;
@@ -1317,10 +1330,14 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   };
 
   // ---- k == 1 fast path: the perturbation support is one sim row ----------
+  // Its accumulation stays separate from value_accum: k = 1 log-weights are
+  // bounded (~35), so it sums W with the f32 exp alone (~20x cheaper than
+  // the software double exp) and takes log(e^s + se) without a multiplicity.
   if (k_obs == 1) {
     const int64_t r = first_obs_r;
     const int32_t x = args.rec_values[r * args.A + a];
-    const float se = self_extra_of(r, x);
+    const float se =
+        value_self_f32(args, p, x, args.collapsed ? args.rec_file[r] : 0);
     double W = 0.0;
     float best = -INFINITY;
     long long best_v = -1;
@@ -1341,8 +1358,6 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         const float s = args.csr_sim[jj];
         const float L = (v == x && se > 0.0f) ? __logf(__expf(s) + se) : s;
         const float logw = log_base_prob(v) + L + __logf(1.0f - __expf(-L));
-        // k = 1 log-weights are bounded (~35), so f32 exp is exact enough and
-        // ~20x cheaper than the software double exp
         W += (double)__expf(logw);
         const float g = gumbel_from_uniform(
             philox_uniform(args.seed, args.iteration, PH_VALG, elem, (uint32_t)v));
@@ -1392,42 +1407,24 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   gover = gbuf[3 * VAL_DMAX] < 0;
   d = gover ? 0 : gbuf[3 * VAL_DMAX];
 
-  // self-extra for a group (or record unit): the collapsed (1/theta - 1)
-  // correction, constant within a (value, file) group
-  auto se_of = [&](int32_t x, int32_t f) -> float {
-    if (!args.collapsed) return 0.0f;
-    const float th = args.theta[a * args.F + f];
-    const float px = args.phi[v0 + x];
-    return (1.0f / th - 1.0f) / (is_const ? px : px * args.norm_lin[v0 + x]);
-  };
   const int n_units = gover ? k_obs : d;
-  // unit u -> (x, multiplicity, file); gover scans the record list
-  auto unit_of = [&](int u, int32_t* x, int32_t* m_, int32_t* f) {
-    if (!gover) {
-      *x = gbuf[u];
-      *f = gbuf[VAL_DMAX + u];
-      *m_ = gbuf[2 * VAL_DMAX + u];
-      return;
-    }
+  // unit u: group u of gbuf, or (gover) the u-th observed record of the list
+  auto unit_of = [&](int u) -> ValueUnit {
+    if (!gover) return {gbuf[u], gbuf[2 * VAL_DMAX + u], gbuf[VAL_DMAX + u]};
     int seen = 0;
     for (int64_t i = r_lo; i < r_hi; ++i) {
       const int64_t r = args.ent_rec_idx[i];
       const int32_t xx = args.rec_values[r * args.A + a];
       if (xx < 0) continue;
-      if (seen++ == u) {
-        *x = xx;
-        *m_ = 1;
-        *f = args.collapsed ? args.rec_file[r] : 0;
-        return;
-      }
+      if (seen++ == u) return {xx, 1, args.collapsed ? args.rec_file[r] : 0};
     }
+    return {0, 0, 0};  // not reached: u < k_obs
   };
 
   // size the table (and its clear/scan cost) to the actual support
   int64_t total_entries = 0;
   for (int u = 0; u < n_units; ++u) {
-    int32_t ux, um, uf;
-    unit_of(u, &ux, &um, &uf);
+    const int32_t ux = unit_of(u).x;
     if (is_const)
       total_entries += 1;
     else
@@ -1464,66 +1461,34 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   long long best_v = -1;
 
   if (VMODE != 2 && !dense) {
-    for (int i = lane; i < tsize; i += WAVE) { keys[i] = -1; vals[i] = 0.0f; }
-    // drain LDS writes before other lanes' atomics may touch the slots
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
+    lds_hash_clear(keys, vals, tsize, lane);
+    const uint32_t mask = (uint32_t)(tsize - 1);
     // hash-accumulate log factors per unit
     for (int u = 0; u < n_units; ++u) {
-      int32_t ux, um, uf;
-      unit_of(u, &ux, &um, &uf);
-      const float self_extra = se_of(ux, uf);
-      const float fm = (float)um;
+      const ValueUnit un = unit_of(u);
+      const float self_extra = value_self_f32(args, p, un.x, un.f);
+      const float fm = (float)un.m;
       if (is_const) {
         // single-entry row {x}: factor = (1 + self_extra)^m
-        if (lane == 0) {
-          float logf_ = fm * __logf(1.0f + self_extra);
-          uint32_t h = ((uint32_t)ux * 2654435761u) & (tsize - 1);
-          while (true) {
-            int32_t prev = atomicCAS(&keys[h], -1, ux);
-            if (prev == -1 || prev == ux) { atomicAdd(&vals[h], logf_); break; }
-            h = (h + 1) & (tsize - 1);
-          }
-        }
+        if (lane == 0)
+          lds_hash_add(keys, vals, mask, un.x, fm * __logf(1.0f + self_extra));
       } else {
-        const int64_t row_lo = args.csr_row_ptr[v0 + ux];
-        const int64_t row_hi = args.csr_row_ptr[v0 + ux + 1];
+        const int64_t row_lo = args.csr_row_ptr[v0 + un.x];
+        const int64_t row_hi = args.csr_row_ptr[v0 + un.x + 1];
         for (int64_t j = row_lo + lane; j < row_hi; j += WAVE) {
           const int32_t v = args.csr_col[j];
-          const float s = args.csr_sim[j];  // log expsim > 0
-          float factor_log = (v == ux && self_extra > 0.0f)
-                                 ? fm * __logf(__expf(s) + self_extra)
-                                 : fm * s;
-          uint32_t h = ((uint32_t)v * 2654435761u) & (tsize - 1);
-          while (true) {
-            int32_t prev = atomicCAS(&keys[h], -1, v);
-            if (prev == -1 || prev == v) { atomicAdd(&vals[h], factor_log); break; }
-            h = (h + 1) & (tsize - 1);
-          }
+          lds_hash_add(keys, vals, mask, v,
+                       row_factor_log(v, un.x, args.csr_sim[j], fm, self_extra));
         }
       }
       __builtin_amdgcn_wave_barrier();
     }
-    // drain all LDS atomics before cross-lane reads of the table
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_wave_barrier();
-    // transform + reduce + gumbel-max over occupied slots
-    for (int i = lane; i < tsize; i += WAVE) {
-      const int32_t v = keys[i];
-      if (v < 0) continue;
-      const float L = vals[i];
-      // log(exp(L) - 1) = L + log1p(-exp(-L)), stable for L > 0
-      const float log_expm1 = L + __logf(1.0f - __expf(-L));
-      const float logw = log_base_prob(v) + log_expm1;
-      W += (logw < 80.0f) ? (double)__expf(logw) : exp((double)logw);
-      const float g = gumbel_from_uniform(
-          philox_uniform(args.seed, args.iteration, PH_VALG, elem, (uint32_t)v));
-      if (logw + g > best) { best = logw + g; best_v = v; }
-    }
+    lds_hash_reduce(args, elem, keys, vals, tsize, lane, log_base_prob, W, best,
+                    best_v);
   } else if (VMODE != 1 && !gover && !is_const && args.vchunk) {
     // chunked hash-accumulate (union too big for one LDS table): sweep the
     // d rows in ascending value-range chunks sized so each chunk's entries
-    // fit the table, then run the same insert/transform/reduce as the small
+    // fit the table, then run the same clear/insert/reduce as the small
     // path per chunk. Replaces the union-merge path's (d-1) dependent-load
     // binary searches PER ENTRY with one binary search per unit PER CHUNK.
     // L_v accumulation order per value (ascending unit) matches the small
@@ -1535,7 +1500,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         const int64_t lo2 = args.csr_row_ptr[v0 + x2];
         glo[u] = args.csr_row_ptr[v0 + x2 + 1];
         gn[u] = (int32_t)(glo[u] - lo2);
-        gse[u] = se_of(x2, gbuf[VAL_DMAX + u]);
+        gse[u] = value_self_f32(args, p, x2, gbuf[VAL_DMAX + u]);
       }
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1557,9 +1522,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         }
       }
       if (!any) break;
-      for (int i = lane; i < HASH_CAP; i += WAVE) { keys[i] = -1; vals[i] = 0.0f; }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
+      lds_hash_clear(keys, vals, HASH_CAP, lane);
       for (int u = 0; u < n_units; ++u) {
         const int64_t end2 = glo[u];
         const int64_t cu = end2 - gn[u];
@@ -1571,33 +1534,14 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         const float fm = (float)gbuf[2 * VAL_DMAX + u];
         for (int64_t j = cu + lane; j < seg_end; j += WAVE) {
           const int32_t v = args.csr_col[j];
-          const float s = args.csr_sim[j];
-          const float factor_log = (v == ux && self_extra > 0.0f)
-                                       ? fm * __logf(__expf(s) + self_extra)
-                                       : fm * s;
-          uint32_t h = ((uint32_t)v * 2654435761u) & (HASH_CAP - 1);
-          while (true) {
-            const int32_t prev = atomicCAS(&keys[h], -1, v);
-            if (prev == -1 || prev == v) { atomicAdd(&vals[h], factor_log); break; }
-            h = (h + 1) & (HASH_CAP - 1);
-          }
+          lds_hash_add(keys, vals, HASH_CAP - 1, v,
+                       row_factor_log(v, ux, args.csr_sim[j], fm, self_extra));
         }
         if (lane == 0) gn[u] = (int32_t)(end2 - seg_end);
         __builtin_amdgcn_wave_barrier();
       }
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_wave_barrier();
-      for (int i = lane; i < HASH_CAP; i += WAVE) {
-        const int32_t v = keys[i];
-        if (v < 0) continue;
-        const float L = vals[i];
-        const float log_expm1 = L + __logf(1.0f - __expf(-L));
-        const float logw = log_base_prob(v) + log_expm1;
-        W += (logw < 80.0f) ? (double)__expf(logw) : exp((double)logw);
-        const float g = gumbel_from_uniform(
-            philox_uniform(args.seed, args.iteration, PH_VALG, elem, (uint32_t)v));
-        if (logw + g > best) { best = logw + g; best_v = v; }
-      }
+      lds_hash_reduce(args, elem, keys, vals, HASH_CAP, lane, log_base_prob, W,
+                      best, best_v);
       // reads of this chunk's table must drain before the next chunk's clear
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_wave_barrier();
@@ -1615,36 +1559,38 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         const int32_t x2 = gbuf[u];
         glo[u] = args.csr_row_ptr[v0 + x2];
         gn[u] = (int32_t)(args.csr_row_ptr[v0 + x2 + 1] - glo[u]);
-        gse[u] = se_of(x2, gbuf[VAL_DMAX + u]);
+        gse[u] = value_self_f32(args, p, x2, gbuf[VAL_DMAX + u]);
       }
     }
+    // unit u2 as the entry loop needs it: the hoisted LDS copy, or (gover)
+    // rebuilt from the record scan
+    struct MergeUnit { int32_t x, m; float se; int64_t lo, hi; };
+    auto merge_unit = [&](int u2) -> MergeUnit {
+      if (hoist) {
+        const int64_t lo2 = glo[u2];
+        return {gbuf[u2], gbuf[2 * VAL_DMAX + u2], gse[u2], lo2, lo2 + gn[u2]};
+      }
+      const ValueUnit un = unit_of(u2);
+      return {un.x, un.m, value_self_f32(args, p, un.x, un.f),
+              args.csr_row_ptr[v0 + un.x], args.csr_row_ptr[v0 + un.x + 1]};
+    };
     for (int u = 0; u < n_units; ++u) {
-      int32_t ux, um, uf;
-      unit_of(u, &ux, &um, &uf);
+      const ValueUnit un = unit_of(u);
+      const int32_t ux = un.x;
       if (is_const) {
         if (lane == 0) {
           bool first = true;
-          for (int u2 = 0; u2 < u && first; ++u2) {
-            int32_t x2, m2, f2;
-            unit_of(u2, &x2, &m2, &f2);
-            if (x2 == ux) first = false;  // only possible when gover
-          }
+          for (int u2 = 0; u2 < u && first; ++u2)
+            if (unit_of(u2).x == ux) first = false;  // only possible when gover
           if (first) {
             float L = 0.0f;
             for (int u2 = u; u2 < n_units; ++u2) {
-              int32_t x2, m2, f2;
-              unit_of(u2, &x2, &m2, &f2);
-              if (x2 != ux) continue;
-              L += (float)m2 * __logf(1.0f + se_of(x2, f2));
+              const ValueUnit o = unit_of(u2);
+              if (o.x != ux) continue;
+              L += (float)o.m * __logf(1.0f + value_self_f32(args, p, o.x, o.f));
             }
-            if (L > 0.0f) {
-              const float log_expm1 = L + __logf(1.0f - __expf(-L));
-              const float logw = log_base_prob(ux) + log_expm1;
-              W += (logw < 80.0f) ? (double)__expf(logw) : exp((double)logw);
-              const float g = gumbel_from_uniform(philox_uniform(
-                  args.seed, args.iteration, PH_VALG, elem, (uint32_t)ux));
-              if (logw + g > best) { best = logw + g; best_v = ux; }
-            }
+            if (L > 0.0f)
+              value_accum(args, elem, ux, L, log_base_prob(ux), W, best, best_v);
           }
         }
         continue;
@@ -1659,50 +1605,26 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
         bool first = true;
         float L = 0.0f;
         for (int u2 = 0; u2 < n_units; ++u2) {
-          int32_t x2, m2;
-          float se2;
+          const MergeUnit o = merge_unit(u2);
           float s2;
-          if (hoist) {
-            x2 = gbuf[u2];
-            m2 = gbuf[2 * VAL_DMAX + u2];
-            se2 = gse[u2];
-            if (u2 == u) {
-              s2 = args.csr_sim[j];
-            } else {
-              const int64_t lo2 = glo[u2];
-              const int64_t hi2 = lo2 + gn[u2];
-              const int64_t p2 = lower_bound_i32(args.csr_col, lo2, hi2, v);
-              const bool found = p2 < hi2 && args.csr_col[p2] == v;
-              if (found && u2 < u) { first = false; break; }
-              s2 = found ? args.csr_sim[p2] : 0.0f;
-            }
+          if (u2 == u) {
+            s2 = args.csr_sim[j];
           } else {
-            int32_t f2;
-            unit_of(u2, &x2, &m2, &f2);
-            if (u2 == u) {
-              s2 = args.csr_sim[j];
-            } else {
-              const int64_t lo2 = args.csr_row_ptr[v0 + x2];
-              const int64_t hi2 = args.csr_row_ptr[v0 + x2 + 1];
-              const int64_t p2 = lower_bound_i32(args.csr_col, lo2, hi2, v);
-              const bool found = p2 < hi2 && args.csr_col[p2] == v;
-              if (found && u2 < u) { first = false; break; }
-              s2 = found ? args.csr_sim[p2] : 0.0f;
-            }
-            se2 = se_of(x2, f2);
+            const int64_t p2 = lower_bound_i32(args.csr_col, o.lo, o.hi, v);
+            const bool found = p2 < o.hi && args.csr_col[p2] == v;
+            if (found && u2 < u) { first = false; break; }
+            s2 = found ? args.csr_sim[p2] : 0.0f;
           }
-          if (v == x2 && se2 > 0.0f)
-            L += (float)m2 * __logf(__expf(s2) + se2);
+          // row_factor_log's two cases, each added to L in its own statement:
+          // the compiler may contract either product with the sum, which
+          // one shared select-then-add need not reproduce bit for bit
+          if (v == o.x && o.se > 0.0f)
+            L += (float)o.m * __logf(__expf(s2) + o.se);
           else if (s2 != 0.0f)
-            L += (float)m2 * s2;
+            L += (float)o.m * s2;
         }
         if (!first) continue;
-        const float log_expm1 = L + __logf(1.0f - __expf(-L));
-        const float logw = log_base_prob(v) + log_expm1;
-        W += (logw < 80.0f) ? (double)__expf(logw) : exp((double)logw);
-        const float g = gumbel_from_uniform(
-            philox_uniform(args.seed, args.iteration, PH_VALG, elem, (uint32_t)v));
-        if (logw + g > best) { best = logw + g; best_v = v; }
+        value_accum(args, elem, v, L, log_base_prob(v), W, best, best_v);
       }
     }
   }
@@ -1713,6 +1635,38 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   finish(W, best, best_v);
 }
 
+template <int VMODE>
+__global__ void __launch_bounds__(WAVES_PER_BLOCK_VAL * WAVE)
+value_update_kernel_t(ValueArgs args) {
+  ctrl_override(args.ctrl, args.seed, args.iteration);
+  __shared__ int32_t h_key[WAVES_PER_BLOCK_VAL][HASH_CAP];
+  __shared__ float h_val[WAVES_PER_BLOCK_VAL][HASH_CAP];
+  __shared__ int32_t g_buf[WAVES_PER_BLOCK_VAL][3 * VAL_DMAX + 1];
+  // merge-path per-unit hoists: (row_lo, row_len, se) per distinct group
+  __shared__ int64_t g_lo[WAVES_PER_BLOCK_VAL][VAL_DMAX];
+  __shared__ int32_t g_n[WAVES_PER_BLOCK_VAL][VAL_DMAX];
+  __shared__ float g_se[WAVES_PER_BLOCK_VAL][VAL_DMAX];
+
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t widx = (int64_t)blockIdx.x * WAVES_PER_BLOCK_VAL + wave;
+  if (args.pair_list != nullptr) {
+    if (widx >= args.n_pairs) return;
+    value_update_pair<VMODE>(args, args.pair_list[widx], lane, h_key[wave],
+                             h_val[wave], g_buf[wave], g_lo[wave], g_n[wave],
+                             g_se[wave]);
+  } else {
+    // kobs self-selection: each wave examines VAL_STRIDE consecutive pairs
+    // and runs the (rare) k >= 2 ones serially
+    const int64_t p0 = widx * VAL_STRIDE;
+    for (int64_t pair = p0; pair < p0 + VAL_STRIDE && pair < args.n_pairs; ++pair) {
+      if (args.kobs[pair] >= 2)
+        value_update_pair<VMODE>(args, pair, lane, h_key[wave], h_val[wave],
+                                 g_buf[wave], g_lo[wave], g_n[wave], g_se[wave]);
+    }
+  }
+}
+
 // Brute-force dense value update (Gibbs-Sequential, GibbsUpdates.scala:652-698)
 __global__ void value_update_seq_kernel(ValueArgs args) {
   ctrl_override(args.ctrl, args.seed, args.iteration);
@@ -1720,12 +1674,11 @@ __global__ void value_update_seq_kernel(ValueArgs args) {
   const int wave = threadIdx.x / WAVE;
   const int64_t pair = (int64_t)blockIdx.x * (blockDim.x / WAVE) + wave;
   if (pair >= args.n_pairs) return;
-  const int64_t e = pair / args.A;
-  const int a = (int)(pair % args.A);
-  const bool is_const = args.attr_const[a];
-  const int64_t v0 = args.voff[a];
-  const int V = (int)(args.voff[a + 1] - v0);
-  const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
+  const ValuePair p = value_pair_of(args, pair);
+  const int64_t e = p.e, v0 = p.v0;
+  const int a = p.a, V = p.V;
+  const bool is_const = p.is_const;
+  const uint64_t elem = p.elem;
 
   const int64_t r_lo = args.ent_rec_ptr[e], r_hi = args.ent_rec_ptr[e + 1];
   int k_obs = 0;
@@ -1744,7 +1697,7 @@ __global__ void value_update_seq_kernel(ValueArgs args) {
   if (k_obs == 0 || is_const) {
     float u1, u2;
     philox_uniform2(args.seed, args.iteration, PH_VALM, elem, 0xFFFF0000u, &u1, &u2);
-    int v = alias_draw(args.phi_prob + v0, args.phi_alias + v0, V, u1, u2);
+    int v = value_base_alias(args, p, 0, u1, u2);
     if (lane == 0) args.ent_values[e * args.A + a] = (int32_t)v;
     return;
   }
@@ -2872,69 +2825,51 @@ void value_update(
       Kc, collapsed, seed, iteration, ent_id_base, error_count, csr_excl,
       csr_rawsum, z1);
   args.ctrl = ctrl.numel() ? ctrl.data_ptr<int64_t>() : nullptr;
+  const auto stream = at::cuda::getCurrentCUDAStream();
+  // thread-per-pair kernels: one thread per entry of the current pair range
+  auto launch_threads = [&](void (*kernel)(ValueArgs)) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((args.n_pairs + 255) / 256)),
+                       dim3(256), 0, stream, args);
+  };
+  // wave kernels: n_waves waves, WAVES_PER_BLOCK_VAL per block
+  auto launch_waves = [&](void (*kernel)(ValueArgs), int64_t n_waves) {
+    hipLaunchKernelGGL(kernel,
+                       dim3((unsigned)wave_grid(n_waves, WAVES_PER_BLOCK_VAL)),
+                       dim3(WAVES_PER_BLOCK_VAL * WAVE), 0, stream, args);
+  };
   if (sequential) {
     const int64_t pairs = args.E * args.A;
     if (pairs == 0) return;
     args.pair_list = nullptr;
     args.n_pairs = pairs;
-    dim3 grid((unsigned)wave_grid(pairs, 4));
-    hipLaunchKernelGGL(value_update_seq_kernel, grid, dim3(4 * WAVE), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
+    launch_waves(value_update_seq_kernel, pairs);
     return;
   }
   if (kobs.numel() > 0) {
     // kobs self-selection: no host-side pair lists, no stream sync — the
-    // four kernels each cover every pair and act only on their class
-    // (k=0 base, k=1, k>=2 hash, k>=2 union-merge)
+    // kernels each cover every pair and act only on their class (k=0 base,
+    // k=1, k>=2 table kd1/kd2, k>=2 hash, k>=2 union-merge)
     args.kobs = kobs.data_ptr<int32_t>();
     args.n_pairs = kobs.numel();
-    dim3 tgrid((unsigned)((args.n_pairs + 255) / 256));
-    hipLaunchKernelGGL(value_base_draw_kernel, tgrid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-    hipLaunchKernelGGL(value_update_k1_kernel, tgrid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-    if (args.tab_excl != nullptr)
-      hipLaunchKernelGGL(value_update_kd1_kernel, tgrid, dim3(256), 0,
-                         at::cuda::getCurrentCUDAStream(), args);
-    if (args.tab2_excl != nullptr) {
-      const int64_t nw2 = (args.n_pairs + 7) / 8;
-      hipLaunchKernelGGL(value_update_kd2_kernel,
-                         dim3((unsigned)wave_grid(nw2, WAVES_PER_BLOCK_VAL)),
-                         dim3(WAVES_PER_BLOCK_VAL * WAVE), 0,
-                         at::cuda::getCurrentCUDAStream(), args);
-    }
+    launch_threads(value_base_draw_kernel);
+    launch_threads(value_update_k1_kernel);
+    if (args.tab_excl != nullptr) launch_threads(value_update_kd1_kernel);
+    if (args.tab2_excl != nullptr)
+      launch_waves(value_update_kd2_kernel, (args.n_pairs + 7) / 8);
     const int64_t n_waves = (args.n_pairs + VAL_STRIDE - 1) / VAL_STRIDE;
-    dim3 wgrid((unsigned)wave_grid(n_waves, WAVES_PER_BLOCK_VAL));
-    hipLaunchKernelGGL(value_update_kernel_t<1>, wgrid,
-                       dim3(WAVES_PER_BLOCK_VAL * WAVE), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-    hipLaunchKernelGGL(value_update_kernel_t<2>, wgrid,
-                       dim3(WAVES_PER_BLOCK_VAL * WAVE), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
+    launch_waves(value_update_kernel_t<1>, n_waves);
+    launch_waves(value_update_kernel_t<2>, n_waves);
     return;
   }
   // explicit pair lists (tests / special cases)
-  if (base_pairs.numel() > 0) {
-    args.pair_list = base_pairs.data_ptr<int64_t>();
-    args.n_pairs = base_pairs.numel();
-    dim3 grid((unsigned)((args.n_pairs + 255) / 256));
-    hipLaunchKernelGGL(value_base_draw_kernel, grid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-  }
-  if (k1_pairs.numel() > 0) {
-    args.pair_list = k1_pairs.data_ptr<int64_t>();
-    args.n_pairs = k1_pairs.numel();
-    dim3 grid((unsigned)((args.n_pairs + 255) / 256));
-    hipLaunchKernelGGL(value_update_k1_kernel, grid, dim3(256), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-  }
-  if (wave_pairs.numel() > 0) {
-    args.pair_list = wave_pairs.data_ptr<int64_t>();
-    args.n_pairs = wave_pairs.numel();
-    dim3 grid((unsigned)wave_grid(args.n_pairs, WAVES_PER_BLOCK_VAL));
-    hipLaunchKernelGGL(value_update_kernel_t<0>, grid, dim3(WAVES_PER_BLOCK_VAL * WAVE), 0,
-                       at::cuda::getCurrentCUDAStream(), args);
-  }
+  auto use_list = [&](const torch::Tensor& pairs) {
+    args.pair_list = pairs.data_ptr<int64_t>();
+    args.n_pairs = pairs.numel();
+    return args.n_pairs > 0;
+  };
+  if (use_list(base_pairs)) launch_threads(value_base_draw_kernel);
+  if (use_list(k1_pairs)) launch_threads(value_update_k1_kernel);
+  if (use_list(wave_pairs)) launch_waves(value_update_kernel_t<0>, args.n_pairs);
 }
 
 void distortion_update(

@@ -9,6 +9,8 @@ exact fp64 probabilities computed in numpy. Deterministic kernels
 tolerance.
 """
 
+import functools
+
 import numpy as np
 import pytest
 
@@ -1176,6 +1178,23 @@ def test_value_kd2_kernel_distribution():
     C.set_value_k2tables(z, z, 0)
 
 
+@functools.lru_cache(maxsize=None)
+def _mutation_ball_model():
+    """(cache, model) over a 650-name mutation ball at threshold 7: every pair
+    within edit distance 4, so sim rows are ~V long (609 rows of 262-384
+    entries, 41 of 650). Built once per session (the pure-Python pair sweep
+    takes ~11 s); callers must not modify the returned model."""
+    rng = np.random.default_rng(11)
+    base = list("ABCABCABCA")
+    pool = set()
+    while len(pool) < 650:
+        s = base.copy()
+        for _ in range(rng.integers(1, 3)):
+            s[rng.integers(0, 10)] = "ABCDE"[rng.integers(0, 5)]
+        pool.add("".join(s))
+    return make_model(DEV, threshold=7.0, names=sorted(pool))
+
+
 @gpu
 def test_value_dense_merge_distribution():
     """k=2 clusters over TWO distinct values whose sim rows overflow the LDS
@@ -1184,16 +1203,7 @@ def test_value_dense_merge_distribution():
     frequencies vs the exact fp64 mixture (GibbsUpdates.scala:533-570):
     w(v) = base2(v) * (f_x1(v) * f_x2(v) - 1), f_x(x) boosted by the
     collapsed self term."""
-    rng = np.random.default_rng(11)
-    # mutation ball: every pair within edit distance 4 -> sim rows ~ V long
-    base = list("ABCABCABCA")
-    pool = set()
-    while len(pool) < 650:
-        s = base.copy()
-        for _ in range(rng.integers(1, 3)):
-            s[rng.integers(0, 10)] = "ABCDE"[rng.integers(0, 5)]
-        pool.add("".join(s))
-    cache, model = make_model(DEV, threshold=7.0, names=sorted(pool))
+    cache, model = _mutation_ball_model()
     a = 1
     idx = cache.indexed_attributes[a].index
     V = idx.num_values
@@ -1207,7 +1217,7 @@ def test_value_dense_merge_distribution():
         row_lens[x1], row_lens[x2])
 
     th = 0.1
-    model.theta.copy_(torch.full((2, 1), th))
+    theta = torch.full((2, 1), th, dtype=torch.float32, device=DEV)
     N = 80000
     # N entities, each with one record of value x1 and one of x2 (file 0)
     rv = np.full((2 * N, 2), -1, dtype=np.int32)
@@ -1227,7 +1237,7 @@ def test_value_dense_merge_distribution():
         _dev(rv, torch.int32), _dev(rec_dist, torch.uint8),
         _dev(np.zeros(2 * N, np.int32), torch.int32),
         _dev(ent_rec_ptr, torch.int64), _dev(ent_rec_idx, torch.int64), ev,
-        model.theta, model.phi, model.log_phi, model.norm_lin, model.log_norm,
+        theta, model.phi, model.log_phi, model.norm_lin, model.log_norm,
         model.voff, model.csr_row_ptr, model.csr_col, model.csr_sim,
         model.phi_prob, model.phi_alias, model.pow_prob, model.pow_alias,
         model.pow_off, model.log_pow_total, model.attr_const, model.Kc,
@@ -1252,3 +1262,100 @@ def test_value_dense_merge_distribution():
     exact = (base2 + w) / (1.0 + W)
     emp = np.bincount(sel, minlength=V) / N
     assert tv_distance(emp, exact) < 0.05, tv_distance(emp, exact)
+
+
+@gpu
+def test_value_pairlist_and_kobs_paths_agree_bitwise(monkeypatch):
+    """Explicit pair-list mode (value_update_kernel_t<0>) and kobs
+    self-selection mode (kernel_t<1>, kernel_t<2>, value_base_draw_kernel)
+    run one value_update_pair body on every k >= 2 pair and draw k = 0 pairs
+    from phi under one Philox tag, so with the k-tables cleared and no k = 1
+    pair the two modes must return identical ent_values. Seven pair classes
+    of 64 entities route through every k >= 2 path: (a) d=1 hash, (b) d=2
+    hash, (c) two 650-entry rows (dense), (d) three short rows (dense),
+    (e) one value in two files (two groups), (f) 17 distinct rows (more than
+    VAL_DMAX groups and k > Kc), (g) k = 0. Checked at DBLINK_VCHUNK=1
+    (chunked hash) and 0 (union merge); the two settings sum W in different
+    orders and need not agree with each other. 64 draws per class over
+    ~300-1300 support values are far too few for a frequency comparison
+    within multinomial noise, so union-merge correctness rests on this
+    bitwise check plus the distribution tests above."""
+    cache, model = _mutation_ball_model()
+    z = torch.empty(0, dtype=torch.float64)
+    C.set_value_ktables(z, z, torch.empty(0, dtype=torch.float32), 0, 0)
+    C.set_value_k2tables(z, z, 0)
+
+    A, a, NC = 2, 1, 64
+    row_lens = np.diff(cache.indexed_attributes[a].index.sim_index.row_ptr)
+    order = np.argsort(row_lens, kind="stable")
+    short = order[row_lens[order] < 650]
+    long_ = order[row_lens[order] == 650]
+    assert len(short) >= NC + 17 and len(long_) >= 2
+
+    # per class: entity i -> list of (name value, file)
+    classes = {
+        "a": lambda i: [(short[i], 0)] * 2,
+        "b": lambda i: [(short[i], 0), (short[i + 1], 0)],
+        "c": lambda i: [(long_[i % len(long_)], 0), (long_[(i + 1) % len(long_)], 0)],
+        "d": lambda i: [(short[i + j], 0) for j in range(3)],
+        "e": lambda i: [(short[i], 0), (short[i], 1)],
+        "f": lambda i: [(short[i + j], 0) for j in range(17)],
+        "g": lambda i: [],
+    }
+    rv, rf, ptr, entries, cls_of = [], [], [0], [], []
+    for name, recs_of in classes.items():
+        for i in range(NC):
+            recs = recs_of(i)
+            for j, (x, f) in enumerate(recs):
+                rv.append([(len(ptr) + j) % 10, int(x)])  # both attributes observed
+                rf.append(f)
+            ptr.append(len(rv))
+            # the kernel's total_entries: one row per distinct (value, file) group
+            entries.append(sum(int(row_lens[x]) for x, f in set(recs)))
+            cls_of.append(name)
+    E, R = len(cls_of), len(rv)
+    entries, cls_of = np.array(entries), np.array(cls_of)
+    kobs = np.repeat(np.diff(ptr), A).astype(np.int32)  # [E*A]
+    # non-vacuity (HASH_CAP = 1024: the hash path holds <= 768 entries)
+    assert (entries[np.isin(cls_of, ["a", "b", "e"])] <= 768).all()
+    assert (entries[np.isin(cls_of, ["a", "b", "e"])] > 0).all()
+    assert (entries[np.isin(cls_of, ["c", "d", "f"])] > 768).all()
+    assert not (kobs == 1).any()
+    assert (kobs[cls_of.repeat(A) == "f"] > model.Kc).all()
+
+    theta = _dev(np.array([[0.05, 0.2], [0.1, 0.3]]), torch.float32)  # [A, F=2]
+    t_rv = _dev(np.array(rv, dtype=np.int32).reshape(R, A), torch.int32)
+    t_rd = torch.ones((R, A), dtype=torch.uint8, device=DEV)
+    t_rf = _dev(np.array(rf, dtype=np.int32), torch.int32)
+    t_ptr = _dev(np.array(ptr, dtype=np.int64), torch.int64)
+    t_idx = torch.arange(R, dtype=torch.int64, device=DEV)
+    empty64 = torch.empty(0, dtype=torch.int64, device=DEV)
+    all_pairs = torch.arange(E * A, dtype=torch.int64, device=DEV)
+    no_kobs = torch.empty(0, dtype=torch.int32, device=DEV)
+    t_kobs = _dev(kobs, torch.int32)
+
+    def run(wave_pairs, kobs_t):
+        ev = torch.zeros((E, A), dtype=torch.int32, device=DEV)
+        err = torch.zeros(1, dtype=torch.int32, device=DEV)
+        C.value_update(
+            t_rv, t_rd, t_rf, t_ptr, t_idx, ev,
+            theta, model.phi, model.log_phi, model.norm_lin, model.log_norm,
+            model.voff, model.csr_row_ptr, model.csr_col, model.csr_sim,
+            model.phi_prob, model.phi_alias, model.pow_prob, model.pow_alias,
+            model.pow_off, model.log_pow_total, model.attr_const, model.Kc,
+            1, 0, 2718, 3, 0, err, wave_pairs, empty64, empty64,
+            model.csr_excl, model.csr_rawsum, model.z1, empty64, kobs_t)
+        torch.cuda.synchronize()
+        return ev.cpu()
+
+    for vchunk in ("1", "0"):
+        monkeypatch.setenv("DBLINK_VCHUNK", vchunk)
+        by_list = run(all_pairs, no_kobs)
+        by_kobs = run(empty64, t_kobs)
+        differ = (by_list != by_kobs).any(dim=1).numpy()
+        print(f"DBLINK_VCHUNK={vchunk}: differing entities per class",
+              {c: int(differ[cls_of == c].sum()) for c in classes},
+              "nonzero fraction", float((by_list != 0).float().mean()))
+        assert torch.equal(by_list, by_kobs), (vchunk, sorted(set(cls_of[differ])))
+        assert (by_list != 0).float().mean() > 0.5
+        assert (by_kobs != 0).float().mean() > 0.5
