@@ -504,8 +504,11 @@ def native_limit_problems(project, table=None):
     Returns (errors, warnings). Errors are limits the GPU engine cannot run
     past (kernels.hip MAX_ATTRS; migration distortion bitmask); warnings are
     documented degradations (CPU fallback of the V x V similarity sweep above
-    64-byte values; byte-level edit distance above 255 distinct characters).
+    256-character values; pure-Python fallback above 65535 distinct
+    characters).
     """
+    from ..ops import SIM_GPU_MAX_LEN, SIM_MAX_SYMBOLS
+
     errors, warnings = [], []
     A = len(project.matching_attributes)
     if A > 16:
@@ -521,20 +524,19 @@ def native_limit_problems(project, table=None):
             vals = [v for v in set(table.columns[ai].tolist()) if v is not None]
             charset = {ch for v in vals for ch in v}
             maxlen = max((len(v) for v in vals), default=0)
-            if len(charset) > 255:
+            if len(charset) > SIM_MAX_SYMBOLS:
                 warnings.append(
                     f"attribute {attr.name!r} has {len(charset)} distinct "
-                    "characters (> 255): the native similarity pass computes "
-                    "BYTE-level (UTF-8) edit distance there, which can differ "
-                    "from the reference's character-level distance "
-                    "(SimilarityFn.scala:92-98) for multi-byte characters"
+                    f"characters (> {SIM_MAX_SYMBOLS}): the native similarity "
+                    "sweeps cannot encode it and the V x V sweep runs in pure "
+                    "Python — identical results, far slower index build"
                 )
-            elif maxlen > 64:
+            elif maxlen > SIM_GPU_MAX_LEN:
                 warnings.append(
                     f"attribute {attr.name!r} has values up to {maxlen} "
-                    "characters (> 64): the V x V similarity sweep runs on "
-                    "the CPU (OpenMP) pass instead of the GPU kernel — "
-                    "identical results, slower index build"
+                    f"characters (> {SIM_GPU_MAX_LEN}): the V x V similarity "
+                    "sweep runs on the CPU (OpenMP) pass instead of the GPU "
+                    "kernel — identical results, slower index build"
                 )
     return errors, warnings
 

@@ -13,6 +13,7 @@ Policy:
 
 from __future__ import annotations
 
+import os
 
 import numpy as np
 
@@ -39,6 +40,27 @@ def native():
     return _C
 
 
+SIM_GPU_MAX_LEN = 256  # sim_pairs_kernel: four 64-bit Myers words per pattern
+SIM_MAX_SYMBOLS = 65535  # 16-bit symbol ids, 0 reserved for padding
+
+
+def sim_pairs_route(num_values, max_len, num_symbols, cuda_available):
+    """Which pass builds a domain's similarity index: ``"gpu"``, ``"cpu"``
+    (native OpenMP) or ``"python"`` (pure-Python oracle).
+
+    The GPU sweep takes domains above ``DBLINK_SIM_GPU_MIN_V`` values
+    (default 8192; below it the launch and transfer overhead outweighs the
+    CPU pass) whose longest value fits ``SIM_GPU_MAX_LEN`` characters. Both
+    native sweeps need the alphabet to fit ``SIM_MAX_SYMBOLS`` ids.
+    """
+    if num_symbols > SIM_MAX_SYMBOLS:
+        return "python"
+    min_v = int(os.environ.get("DBLINK_SIM_GPU_MIN_V", "8192"))
+    if cuda_available and num_values > min_v and max_len <= SIM_GPU_MAX_LEN:
+        return "gpu"
+    return "cpu"
+
+
 def sim_pairs(values, similarity_fn):
     """Build the sparse exp-similarity index over a domain of strings.
 
@@ -53,47 +75,49 @@ def sim_pairs(values, similarity_fn):
         return SimIndexCSR(np.zeros(n + 1, dtype=np.int64), np.empty(0, np.int32), np.empty(0))
 
     # Edit distance must be over CHARACTERS (the reference uses JVM strings,
-    # SimilarityFn.scala:92-98), but the native kernels compare bytes. Encode
-    # through a per-domain character vocabulary: one byte per character, so
-    # byte-level Levenshtein == character-level. Domains with > 255 distinct
-    # characters (not seen in practice) fall back to the python oracle.
+    # SimilarityFn.scala:92-98). Encode through a per-domain character
+    # vocabulary, one symbol id per character (0 pads), so symbol-level
+    # Levenshtein == character-level: uint8 ids up to 255 distinct
+    # characters, 16-bit ids (int16 storage) up to 65535.
     charset = sorted({ch for v in values for ch in v})
-    if _C is not None and hasattr(_C, "sim_pairs_cpu"):
-        lens_list = [len(v) for v in values]
-        if len(charset) <= 255:
-            vocab = {ch: i + 1 for i, ch in enumerate(charset)}
-            rows = [[vocab[ch] for ch in v] for v in values]
-        else:
-            # > 255 distinct characters: keep the native pass on UTF-8 bytes
-            # (a byte-level distance; avoids the quadratic python fallback)
-            import logging
-
-            logging.getLogger("dblink_amd.ops").warning(
-                "attribute domain has %d distinct characters (> 255): computing "
-                "BYTE-level (UTF-8) edit distance, which can differ from the "
-                "reference's character-level distance for multi-byte characters",
-                len(charset),
-            )
-            rows = [list(v.encode("utf-8", "surrogatepass")) for v in values]
-            lens_list = [len(r) for r in rows]
-        lens = np.array(lens_list, dtype=np.int32)
-        maxlen = int(lens.max()) if len(lens) else 0
-        buf = np.zeros((len(values), max(maxlen, 1)), dtype=np.uint8)
-        for i, r in enumerate(rows):
-            buf[i, : len(r)] = r
+    lens = np.array([len(v) for v in values], dtype=np.int32)
+    maxlen = int(lens.max()) if len(lens) else 0
+    cuda = False
+    if _C is not None and hasattr(_C, "sim_pairs_gpu"):
         import torch
+
+        cuda = torch.cuda.is_available()
+    route = sim_pairs_route(len(values), maxlen, len(charset), cuda)
+    if route == "python" and len(charset) > SIM_MAX_SYMBOLS:
+        import logging
+
+        logging.getLogger("dblink_amd.ops").warning(
+            "attribute domain has %d distinct characters (> %d): the native "
+            "similarity sweeps cannot encode it; running the quadratic "
+            "pure-Python pass",
+            len(charset), SIM_MAX_SYMBOLS,
+        )
+    if route != "python" and _C is not None and hasattr(_C, "sim_pairs_cpu"):
+        import torch
+
+        vocab = {ch: i + 1 for i, ch in enumerate(charset)}
+        wide = len(charset) > 255
+        # the GPU kernel's row stride: a multiple of 64 symbols (one Myers word)
+        stride = -(-max(maxlen, 1) // 64) * 64 if route == "gpu" else max(maxlen, 1)
+        buf = np.zeros((len(values), stride), dtype=np.uint16 if wide else np.uint8)
+        for i, v in enumerate(values):
+            buf[i, : len(v)] = [vocab[ch] for ch in v]
+        if wide:
+            buf = buf.view(np.int16)
 
         thr = float(similarity_fn.threshold)
         msim = float(similarity_fn.max_similarity)
         # Large domains: run the V x V sweep on the GPU (the reference's Spark
         # cartesian analog, AttributeIndex.scala:222-231) — the quadratic pair
         # filter is the startup bottleneck at V ~ 10^5.
-        if torch.cuda.is_available() and len(values) > 8192 and maxlen <= 64:
-            dev_buf = torch.from_numpy(buf).cuda()
-            if dev_buf.shape[1] < 64:
-                dev_buf = torch.nn.functional.pad(dev_buf, (0, 64 - dev_buf.shape[1]))
+        if route == "gpu":
             row_ptr, col, expsim = _C.sim_pairs_gpu(
-                dev_buf.contiguous(), torch.from_numpy(lens).cuda(), thr, msim
+                torch.from_numpy(buf).cuda(), torch.from_numpy(lens).cuda(), thr, msim
             )
             # atomically-filled rows are unordered; sort within rows by col
             V = len(values)

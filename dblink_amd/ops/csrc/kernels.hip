@@ -2270,55 +2270,160 @@ __global__ void kd_descent_kernel(
 // One WAVE per value i: the wave builds a Myers bit-parallel Peq table for
 // string i in LDS once, then its 64 lanes sweep candidate values j from the
 // length-bucketed window (sim > 0 bounds |len_i - len_j|). Edit distance via
-// Hyyro's bit-vector recurrence: O(len_j) 64-bit ops per pair instead of the
-// O(len_i * len_j) scratch-array DP — ~25x fewer operations, no scratch.
-constexpr int SP_WAVES = 4;  // waves per block
+// Hyyro's bit-vector recurrence: O(W * len_j) 64-bit ops per pair instead of
+// the O(len_i * len_j) scratch-array DP, no scratch.
+//
+// The pattern (row value i) occupies W = ceil(len_i / 64) words, W compiled
+// in. Rows are launched per length class (<= 64, 65..128, 129..192, 193..256)
+// over that class's contiguous slice of len_order, so short rows always run
+// the single-word instance whatever else the domain holds; the text (value j)
+// may have any length at any W.
+//
+// Symbols are uint8 (direct-indexed 256-entry Peq) or 16-bit ids (per-wave
+// open-addressing table over the pattern's own <= 64*W symbols); id 0 is
+// padding in both and never occurs inside a value.
+constexpr int SP_WAVES = 4;      // waves per block
+constexpr int SP_WAVES_WIDE = 2; // 16-bit symbols at W >= 3 (LDS budget)
+constexpr int SP_MAX_LEN = 256;  // 4 Myers words
 
-__device__ int myers_distance(const unsigned long long* Peq, int m,
-                              const uint8_t* b, int lb) {
+// LDS per wave and the LDS-bound residency on a 160 KiB CU:
+//   uint8   W=1..4: 2/4/6/8 KiB per wave, 4 waves per block
+//           -> 20/10/6/5 blocks = 32/32/24/20 waves per CU
+//   16-bit  W=1,2: 128/256 slots, 1.5/5 KiB per wave, 4 waves per block
+//           -> 32/32 waves per CU
+//           W=3,4: 512 slots, 14/18 KiB per wave, 2 waves per block
+//           -> 5/4 blocks = 10/8 waves per CU
+template <typename Sym, int W>
+struct SimPeq;
+
+template <int W>
+struct SimPeq<uint8_t, W> {
+  static constexpr int WORDS = 256 * W;  // 64-bit words per wave
+  unsigned long long* mask;              // [256][W]
+
+  __device__ explicit SimPeq(unsigned long long* lds) : mask(lds) {}
+  __device__ void clear(int lane) {
+    for (int c = lane; c < WORDS; c += WAVE) mask[c] = 0ull;
+  }
+  __device__ void insert(uint8_t sym, int pos) {
+    atomicOr(&mask[(int)sym * W + (pos >> 6)], 1ull << (pos & 63));
+  }
+  __device__ void lookup(uint8_t sym, unsigned long long (&Eq)[W]) const {
+#pragma unroll
+    for (int w = 0; w < W; ++w) Eq[w] = mask[(int)sym * W + w];
+  }
+};
+
+// Open addressing, linear probing, load <= 1/2 (a pattern of W words has at
+// most 64*W distinct symbols). Key 0 marks an empty slot.
+template <int W>
+struct SimPeq<uint16_t, W> {
+  static constexpr int SLOTS = W == 1 ? 128 : (W == 2 ? 256 : 512);
+  static constexpr int WORDS = SLOTS * W + SLOTS / 2;
+  unsigned long long* mask;  // [SLOTS][W]
+  unsigned int* key;         // [SLOTS]
+
+  __device__ explicit SimPeq(unsigned long long* lds)
+      : mask(lds), key(reinterpret_cast<unsigned int*>(lds + SLOTS * W)) {}
+  __device__ static unsigned slot_of(unsigned sym) {
+    return ((sym * 40503u) >> 4) & (unsigned)(SLOTS - 1);
+  }
+  __device__ void clear(int lane) {
+    for (int c = lane; c < WORDS; c += WAVE) mask[c] = 0ull;
+  }
+  __device__ void insert(uint16_t sym, int pos) {
+    unsigned h = slot_of(sym);
+    for (;;) {
+      const unsigned prev = atomicCAS(&key[h], 0u, (unsigned)sym);
+      if (prev == 0u || prev == (unsigned)sym) break;
+      h = (h + 1u) & (unsigned)(SLOTS - 1);
+    }
+    atomicOr(&mask[(int)h * W + (pos >> 6)], 1ull << (pos & 63));
+  }
+  __device__ void lookup(uint16_t sym, unsigned long long (&Eq)[W]) const {
+    unsigned h = slot_of(sym);
+    for (;;) {
+      const unsigned k = key[h];
+      if (k == (unsigned)sym || k == 0u) break;  // empty slot: masks are 0
+      h = (h + 1u) & (unsigned)(SLOTS - 1);
+    }
+#pragma unroll
+    for (int w = 0; w < W; ++w) Eq[w] = mask[(int)h * W + w];
+  }
+};
+
+// The recurrence on a 64*W-bit integer held as W words: every step is
+// bitwise except the add, which carries word to word, and the Ph/Mh left
+// shifts, which carry their top bit (Ph's low word shifts in 1). The caller
+// guarantees (m-1)/64 == W-1, so the score bit sits in the last word.
+template <typename Sym, int W>
+__device__ int myers_distance(const SimPeq<Sym, W>& peq, int m, const Sym* b, int lb) {
   if (m == 0) return lb;
   int score = m;
-  unsigned long long Pv = ~0ull, Mv = 0ull;
-  const unsigned long long last = 1ull << (m - 1);
+  unsigned long long Pv[W], Mv[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    Pv[w] = ~0ull;
+    Mv[w] = 0ull;
+  }
+  const unsigned long long last = 1ull << ((m - 1) & 63);
   for (int j = 0; j < lb; ++j) {
-    const unsigned long long Eq = Peq[b[j]];
-    const unsigned long long Xv = Eq | Mv;
-    const unsigned long long Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    unsigned long long Ph = Mv | ~(Xh | Pv);
-    unsigned long long Mh = Pv & Xh;
-    if (Ph & last) ++score;
-    if (Mh & last) --score;
-    Ph = (Ph << 1) | 1ull;
-    Mh <<= 1;
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
+    unsigned long long Eq[W];
+    peq.lookup(b[j], Eq);
+    unsigned long long add_c = 0ull, ph_c = 1ull, mh_c = 0ull;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const unsigned long long Xv = Eq[w] | Mv[w];
+      const unsigned long long t = Eq[w] & Pv[w];
+      const unsigned long long s1 = t + Pv[w];
+      const unsigned long long s2 = s1 + add_c;
+      add_c = (unsigned long long)(s1 < t) | (unsigned long long)(s2 < s1);
+      const unsigned long long Xh = (s2 ^ Pv[w]) | Eq[w];
+      unsigned long long Ph = Mv[w] | ~(Xh | Pv[w]);
+      unsigned long long Mh = Pv[w] & Xh;
+      if (w == W - 1) {
+        if (Ph & last) ++score;
+        if (Mh & last) --score;
+      }
+      const unsigned long long ph_o = Ph >> 63, mh_o = Mh >> 63;
+      Ph = (Ph << 1) | ph_c;
+      Mh = (Mh << 1) | mh_c;
+      ph_c = ph_o;
+      mh_c = mh_o;
+      Pv[w] = Mh | ~(Xv | Ph);
+      Mv[w] = Ph & Xv;
+    }
   }
   return score;
 }
 
-__global__ void __launch_bounds__(SP_WAVES * WAVE) sim_pairs_kernel(
-    const uint8_t* __restrict__ strs,  // [V, 64]
+template <typename Sym, int W, int WAVES>
+__global__ void __launch_bounds__(WAVES * WAVE) sim_pairs_kernel(
+    const Sym* __restrict__ strs,      // [V, max_len]
     const int32_t* __restrict__ lens,  // [V]
     const int32_t* __restrict__ len_order,  // [V] value ids sorted by length
-    const int64_t* __restrict__ len_ptr,    // [66] bucket offsets by length
-    int V, int max_len, float threshold, float max_sim,
+    const int64_t* __restrict__ len_ptr,    // [max_len + 2] bucket offsets by length
+    int64_t row_begin, int64_t row_end,     // this class's slice of len_order
+    int max_len, float threshold, float max_sim,
     int64_t* __restrict__ row_counts,  // [V] (pass 1 out) or row offsets (pass 2 in)
     int32_t* __restrict__ out_col,     // pass 2
     float* __restrict__ out_expsim,    // pass 2 (stores exp(sim))
     int64_t* __restrict__ fill_pos,    // [V] atomic cursors (pass 2)
     int fill) {
-  __shared__ unsigned long long peq_block[SP_WAVES][256];
+  __shared__ unsigned long long peq_block[WAVES * SimPeq<Sym, W>::WORDS];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
-  const int i = blockIdx.x * SP_WAVES + wave;
-  if (i >= V) return;
-  unsigned long long* Peq = peq_block[wave];
+  // longest rows of the class first: they carry the widest windows
+  const int64_t r = row_end - 1 - ((int64_t)blockIdx.x * WAVES + wave);
+  if (r < row_begin) return;
+  const int i = len_order[r];
+  SimPeq<Sym, W> peq(peq_block + wave * SimPeq<Sym, W>::WORDS);
   const int la = lens[i];
-  const uint8_t* a = strs + (int64_t)i * max_len;
-  for (int c = lane; c < 256; c += WAVE) Peq[c] = 0ull;
+  const Sym* a = strs + (int64_t)i * max_len;
+  peq.clear(lane);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
-  if (lane < la) atomicOr(&Peq[a[lane]], 1ull << lane);
+  for (int p = lane; p < la; p += WAVE) peq.insert(a[p], p);
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_wave_barrier();
 
@@ -2349,7 +2454,7 @@ __global__ void __launch_bounds__(SP_WAVES * WAVE) sim_pairs_kernel(
       unit = 1.0f;
     } else {
       if ((float)abs(la - lb) >= band * (float)tot) continue;
-      const int d = myers_distance(Peq, la, strs + (int64_t)j * max_len, lb);
+      const int d = myers_distance<Sym, W>(peq, la, strs + (int64_t)j * max_len, lb);
       unit = 1.0f - 2.0f * (float)d / ((float)tot + (float)d);
     }
     const float trans = scale * (max_sim * unit - threshold);
@@ -2991,12 +3096,58 @@ void kd_descent(
                      ent_part_out.data_ptr<int32_t>());
 }
 
+// One pass (count or fill) of the sweep's operands; shapes are on
+// sim_pairs_kernel's parameter list.
+struct SimSweep {
+  const void* strs;
+  const int32_t *lens, *len_order;
+  const int64_t* len_ptr;
+  int max_len;
+  float threshold, max_sim;
+  int64_t* row_counts;
+  int32_t* out_col;
+  float* out_expsim;
+  int64_t* fill_pos;
+  int fill;
+};
+
+template <typename Sym, int W, int WAVES>
+static void launch_sim_class(const SimSweep& s, int64_t row_begin, int64_t row_end) {
+  if (row_end <= row_begin) return;
+  dim3 grid((unsigned)wave_grid(row_end - row_begin, WAVES));
+  hipLaunchKernelGGL((sim_pairs_kernel<Sym, W, WAVES>), grid, dim3(WAVES * WAVE), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     static_cast<const Sym*>(s.strs), s.lens, s.len_order, s.len_ptr,
+                     row_begin, row_end, s.max_len, s.threshold, s.max_sim,
+                     s.row_counts, s.out_col, s.out_expsim, s.fill_pos, s.fill);
+}
+
+// One kernel instance per row-length class; class_ptr[k] is the first
+// len_order position whose length exceeds 64*k.
+template <typename Sym>
+static void launch_sim_sweep(const SimSweep& s, const int64_t (&class_ptr)[5]) {
+  constexpr int WIDE = sizeof(Sym) == 1 ? SP_WAVES : SP_WAVES_WIDE;
+  launch_sim_class<Sym, 1, SP_WAVES>(s, class_ptr[0], class_ptr[1]);
+  launch_sim_class<Sym, 2, SP_WAVES>(s, class_ptr[1], class_ptr[2]);
+  launch_sim_class<Sym, 3, WIDE>(s, class_ptr[2], class_ptr[3]);
+  launch_sim_class<Sym, 4, WIDE>(s, class_ptr[3], class_ptr[4]);
+}
+
 std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
                                          double threshold, double max_sim) {
   CHECK_GPU(strs);
+  CHECK_GPU(lens);
+  TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous(), "strs must be a contiguous [V, stride] tensor");
+  const bool wide = strs.scalar_type() == torch::kInt16 || strs.scalar_type() == torch::kUInt16;
+  TORCH_CHECK(wide || strs.scalar_type() == torch::kUInt8,
+              "strs must hold uint8 symbols or 16-bit symbol ids (int16 storage)");
+  TORCH_CHECK(lens.scalar_type() == torch::kInt32 && lens.is_contiguous() &&
+              lens.numel() == strs.size(0), "lens must be a contiguous int32 [V] tensor");
   const int V = (int)strs.size(0);
   const int max_len = (int)strs.size(1);
-  TORCH_CHECK(max_len <= 64, "attribute values longer than 64 bytes unsupported");
+  TORCH_CHECK(max_len <= SP_MAX_LEN, "sim_pairs_gpu: row stride ", max_len,
+              " exceeds the GPU sweep's limit of ", SP_MAX_LEN,
+              " symbols per value (longer domains take the CPU pass)");
   auto opts_i64 = torch::TensorOptions().dtype(torch::kInt64).device(strs.device());
   // length buckets: candidates for value i live in a contiguous window of
   // the length-sorted order
@@ -3004,16 +3155,37 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
   auto len_order = torch::argsort(lens64, /*stable=*/true).to(torch::kInt32).contiguous();
   auto sorted_lens = std::get<0>(torch::sort(lens64));
   auto len_ptr = torch::searchsorted(
-      sorted_lens, torch::arange(66, opts_i64), /*out_int32=*/false, /*right=*/false)
+      sorted_lens, torch::arange(max_len + 2, opts_i64), /*out_int32=*/false, /*right=*/false)
       .contiguous();
+  // Rows of length 64(k-1)+1 .. 64k form class k (class 1 also holds length
+  // 0). A length outside [0, max_len] falls outside every class and every
+  // candidate window, so such a row comes back empty instead of being read.
+  auto len_ptr_host = len_ptr.cpu();
+  const int64_t* lp = len_ptr_host.data_ptr<int64_t>();
+  int64_t class_ptr[5];
+  class_ptr[0] = lp[0];
+  for (int k = 1; k <= 4; ++k) class_ptr[k] = lp[std::min(64 * k, max_len) + 1];
+
+  SimSweep s;
+  s.strs = strs.data_ptr();
+  s.lens = lens.data_ptr<int32_t>();
+  s.len_order = len_order.data_ptr<int32_t>();
+  s.len_ptr = len_ptr.data_ptr<int64_t>();
+  s.max_len = max_len;
+  s.threshold = (float)threshold;
+  s.max_sim = (float)max_sim;
+  auto sweep = [&]() {
+    if (wide) launch_sim_sweep<uint16_t>(s, class_ptr);
+    else launch_sim_sweep<uint8_t>(s, class_ptr);
+  };
+
   auto row_counts = torch::zeros({V}, opts_i64);
-  dim3 grid((unsigned)((V + SP_WAVES - 1) / SP_WAVES));
-  hipLaunchKernelGGL(sim_pairs_kernel, grid, dim3(SP_WAVES * WAVE), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     strs.data_ptr<uint8_t>(), lens.data_ptr<int32_t>(),
-                     len_order.data_ptr<int32_t>(), len_ptr.data_ptr<int64_t>(),
-                     V, max_len, (float)threshold, (float)max_sim,
-                     row_counts.data_ptr<int64_t>(), nullptr, nullptr, nullptr, 0);
+  s.row_counts = row_counts.data_ptr<int64_t>();
+  s.out_col = nullptr;
+  s.out_expsim = nullptr;
+  s.fill_pos = nullptr;
+  s.fill = 0;
+  sweep();
   auto row_ptr = torch::zeros({V + 1}, opts_i64);
   row_ptr.slice(0, 1, V + 1) = torch::cumsum(row_counts, 0);
   auto row_start = row_ptr.slice(0, 0, V).contiguous();
@@ -3021,13 +3193,12 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
   auto col = torch::empty({nnz}, torch::TensorOptions().dtype(torch::kInt32).device(strs.device()));
   auto expsim = torch::empty({nnz}, torch::TensorOptions().dtype(torch::kFloat32).device(strs.device()));
   auto fill_pos = torch::zeros({V}, opts_i64);
-  hipLaunchKernelGGL(sim_pairs_kernel, grid, dim3(SP_WAVES * WAVE), 0,
-                     at::cuda::getCurrentCUDAStream(),
-                     strs.data_ptr<uint8_t>(), lens.data_ptr<int32_t>(),
-                     len_order.data_ptr<int32_t>(), len_ptr.data_ptr<int64_t>(),
-                     V, max_len, (float)threshold, (float)max_sim,
-                     row_start.data_ptr<int64_t>(), col.data_ptr<int32_t>(),
-                     expsim.data_ptr<float>(), fill_pos.data_ptr<int64_t>(), 1);
+  s.row_counts = row_start.data_ptr<int64_t>();
+  s.out_col = col.data_ptr<int32_t>();
+  s.out_expsim = expsim.data_ptr<float>();
+  s.fill_pos = fill_pos.data_ptr<int64_t>();
+  s.fill = 1;
+  sweep();
   return {row_ptr, col, expsim};
 }
 

@@ -18,9 +18,11 @@ namespace dblink {
 
 // Edit distance with early exit once every cell of a row exceeds `band`
 // (the exact distance is then irrelevant: sim truncates to 0). Attribute
-// values are short (<= 64 bytes), so a plain rolling-array DP with the row-min
-// cutoff is both simple and fast; the big win is the caller's length filter.
-static int levenshtein_capped(const uint8_t* a, int la, const uint8_t* b, int lb,
+// values are short (tens of symbols; any length is accepted), so a plain
+// rolling-array DP with the row-min cutoff is both simple and fast; the big
+// win is the caller's length filter. Sym is uint8_t or a 16-bit symbol id.
+template <typename Sym>
+static int levenshtein_capped(const Sym* a, int la, const Sym* b, int lb,
                               int band, int* scratch) {
   if (la == 0) return lb;
   if (lb == 0) return la;
@@ -30,7 +32,7 @@ static int levenshtein_capped(const uint8_t* a, int la, const uint8_t* b, int lb
   for (int i = 1; i <= la; ++i) {
     cur[0] = i;
     int row_min = i;
-    const uint8_t ca = a[i - 1];
+    const Sym ca = a[i - 1];
     for (int j = 1; j <= lb; ++j) {
       const int cost = (ca == b[j - 1]) ? 0 : 1;
       int m = prev[j - 1] + cost;
@@ -47,13 +49,12 @@ static int levenshtein_capped(const uint8_t* a, int la, const uint8_t* b, int lb
   return prev[lb];
 }
 
-std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim) {
-  TORCH_CHECK(strs.dim() == 2 && strs.dtype() == torch::kUInt8);
-  TORCH_CHECK(lens.dtype() == torch::kInt32);
+template <typename Sym>
+static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::Tensor lens,
+                                                     double threshold, double max_sim) {
   const int64_t V = strs.size(0);
   const int64_t max_len = strs.size(1);
-  const uint8_t* S = strs.data_ptr<uint8_t>();
+  const Sym* S = static_cast<const Sym*>(strs.data_ptr());
   const int32_t* L = lens.data_ptr<int32_t>();
   const double u0 = threshold / max_sim;
   const double scale = max_sim / (max_sim - threshold);
@@ -63,7 +64,7 @@ std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
 
 #pragma omp parallel for schedule(dynamic, 16)
   for (int64_t i = 0; i < V; ++i) {
-    const uint8_t* a = S + i * max_len;
+    const Sym* a = S + i * max_len;
     const int la = L[i];
     std::vector<int> scratch(2 * (max_len + 1));
     for (int64_t j = 0; j < V; ++j) {
@@ -108,6 +109,20 @@ std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
     std::copy(sims[i].begin(), sims[i].end(), sp + rp[i]);
   }
   return {row_ptr, col, expsim};
+}
+
+// strs: [V, stride] uint8 symbols, or 16-bit symbol ids in int16 storage
+// (read as uint16_t); id 0 pads either.
+std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
+                                         double threshold, double max_sim) {
+  TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous() && !strs.is_cuda());
+  TORCH_CHECK(lens.dtype() == torch::kInt32 && lens.is_contiguous() &&
+              lens.numel() == strs.size(0));
+  if (strs.scalar_type() == torch::kUInt8)
+    return sim_pairs_cpu_impl<uint8_t>(strs, lens, threshold, max_sim);
+  TORCH_CHECK(strs.scalar_type() == torch::kInt16 || strs.scalar_type() == torch::kUInt16,
+              "strs must hold uint8 symbols or 16-bit symbol ids (int16 storage)");
+  return sim_pairs_cpu_impl<uint16_t>(strs, lens, threshold, max_sim);
 }
 
 }  // namespace dblink
