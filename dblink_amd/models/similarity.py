@@ -9,6 +9,10 @@ Semantics match the reference (``SimilarityFn.scala:25-107``):
       unit(a,b)  = 1 - 2*d / (|a| + |b| + d)          (1.0 when both empty)
       sim(a,b)   = max(0, t * (S_max * unit(a,b) - thr)),  t = S_max/(S_max-thr)
 
+- ``DamerauLevenshteinSimilarityFn(threshold, maxSimilarity)``: the same with
+  ``d`` the restricted Damerau-Levenshtein (optimal string alignment)
+  distance, which counts an adjacent swap as one edit. Not in the reference.
+
 These host implementations are the *oracle*; the batched V x V domain sweep
 used to build the attribute index runs in the native extension
 (CPU C++ / HIP for gfx950) — see ``dblink_amd.ops``.
@@ -19,6 +23,9 @@ from __future__ import annotations
 
 class SimilarityFn:
     is_constant = False
+    # which native sweep metric (``dblink_amd.ops.sim_pairs``) computes this
+    # function: "levenshtein", "osa", or None for the pure-Python pass
+    native_metric = None
 
     def similarity(self, a: str, b: str) -> float:
         raise NotImplementedError
@@ -64,8 +71,44 @@ def levenshtein(a: str, b: str) -> int:
     return prev[lb]
 
 
-class LevenshteinSimilarityFn(SimilarityFn):
+def osa_distance(a: str, b: str) -> int:
+    """Restricted Damerau-Levenshtein (optimal string alignment) distance.
+
+    The Levenshtein recurrence plus one term: swapping two adjacent
+    characters costs 1, and no substring is edited twice. It is therefore
+    not the unrestricted Damerau distance: ``osa("ca", "abc") == 3`` where
+    unrestricted Damerau gives 2 (swap, then insert between the swapped pair).
+    """
+    la, lb = len(a), len(b)
+    if la == 0:
+        return lb
+    if lb == 0:
+        return la
+    prev2 = None
+    prev = list(range(lb + 1))
+    for i in range(1, la + 1):
+        cur = [i] + [0] * lb
+        ca = a[i - 1]
+        for j in range(1, lb + 1):
+            cost = 0 if ca == b[j - 1] else 1
+            m = min(prev[j] + 1, cur[j - 1] + 1, prev[j - 1] + cost)
+            if i > 1 and j > 1 and ca == b[j - 2] and a[i - 2] == b[j - 1]:
+                m = min(m, prev2[j - 2] + 1)
+            cur[j] = m
+        prev2, prev = prev, cur
+    return prev[lb]
+
+
+class _EditSimilarityFn(SimilarityFn):
+    """Truncated, scaled normalized similarity over an integer edit distance.
+
+    Subclasses set ``_distance`` (the metric), ``_name`` (the config name)
+    and ``native_metric``.
+    """
+
     is_constant = False
+    _distance = None
+    _name = None
 
     def __init__(self, threshold: float = 7.0, max_similarity: float = 10.0):
         if max_similarity <= 0.0:
@@ -80,7 +123,7 @@ class LevenshteinSimilarityFn(SimilarityFn):
         total = len(a) + len(b)
         if total == 0:
             return 1.0
-        d = levenshtein(a, b)
+        d = type(self)._distance(a, b)
         return 1.0 - 2.0 * d / (total + d)
 
     def similarity(self, a: str, b: str) -> float:
@@ -88,17 +131,40 @@ class LevenshteinSimilarityFn(SimilarityFn):
         return s if s > 0.0 else 0.0
 
     def mk_string(self) -> str:
-        return f"LevenshteinSimilarityFn(threshold={self.threshold}, maxSimilarity={self.max_similarity})"
+        return f"{self._name}(threshold={self.threshold}, maxSimilarity={self.max_similarity})"
 
     def __eq__(self, other):
         return (
-            isinstance(other, LevenshteinSimilarityFn)
+            type(other) is type(self)
             and other.threshold == self.threshold
             and other.max_similarity == self.max_similarity
         )
 
     def __hash__(self):
-        return hash(("LevenshteinSimilarityFn", self.threshold, self.max_similarity))
+        return hash((self._name, self.threshold, self.max_similarity))
+
+
+class LevenshteinSimilarityFn(_EditSimilarityFn):
+    native_metric = "levenshtein"
+    _distance = staticmethod(levenshtein)
+    _name = "LevenshteinSimilarityFn"
+
+
+class DamerauLevenshteinSimilarityFn(_EditSimilarityFn):
+    """``LevenshteinSimilarityFn`` with adjacent transpositions at cost 1.
+
+    This is the *restricted* Damerau-Levenshtein distance (optimal string
+    alignment, ``osa_distance``): "jonh"/"john" is 1 edit, not 2, but no
+    substring is edited twice, so ``osa("ca", "abc") == 3`` where the
+    unrestricted Damerau distance is 2.
+    """
+
+    native_metric = "osa"
+    _distance = staticmethod(osa_distance)
+    _name = "DamerauLevenshteinSimilarityFn"
+
+
+_EDIT_FNS = {c._name: c for c in (LevenshteinSimilarityFn, DamerauLevenshteinSimilarityFn)}
 
 
 def similarity_fn_from_config(cfg) -> SimilarityFn:
@@ -106,8 +172,8 @@ def similarity_fn_from_config(cfg) -> SimilarityFn:
     name = cfg.get_string("name")
     if name == "ConstantSimilarityFn":
         return ConstantSimilarityFn()
-    if name == "LevenshteinSimilarityFn":
-        return LevenshteinSimilarityFn(
+    if name in _EDIT_FNS:
+        return _EDIT_FNS[name](
             threshold=cfg.get_double("parameters.threshold"),
             max_similarity=cfg.get_double("parameters.maxSimilarity"),
         )

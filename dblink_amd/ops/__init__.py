@@ -66,7 +66,9 @@ def sim_pairs(values, similarity_fn):
 
     Returns a ``SimIndexCSR``. Replaces the reference's Spark ``cartesian``
     V x V sweep (``AttributeIndex.scala:219-231``) with a length-pruned
-    banded Levenshtein pass.
+    banded edit-distance pass. ``similarity_fn.native_metric`` selects the
+    metric of the native sweeps: ``"levenshtein"``, or ``"osa"`` (adjacent
+    transpositions at cost 1).
     """
     from ..models.attribute_index import SimIndexCSR, _python_sim_pairs
 
@@ -74,10 +76,19 @@ def sim_pairs(values, similarity_fn):
         n = len(values)
         return SimIndexCSR(np.zeros(n + 1, dtype=np.int64), np.empty(0, np.int32), np.empty(0))
 
+    # Only a function that names a native metric may take a native sweep;
+    # any other non-constant function is scored by its own similarity().
+    metric = getattr(similarity_fn, "native_metric", None)
+    if metric is None:
+        return _python_sim_pairs(values, similarity_fn)
+    if metric not in ("levenshtein", "osa"):
+        raise ValueError(f"unknown native similarity metric: {metric!r}")
+    transpositions = metric == "osa"
+
     # Edit distance must be over CHARACTERS (the reference uses JVM strings,
     # SimilarityFn.scala:92-98). Encode through a per-domain character
     # vocabulary, one symbol id per character (0 pads), so symbol-level
-    # Levenshtein == character-level: uint8 ids up to 255 distinct
+    # distance == character-level: uint8 ids up to 255 distinct
     # characters, 16-bit ids (int16 storage) up to 65535.
     charset = sorted({ch for v in values for ch in v})
     lens = np.array([len(v) for v in values], dtype=np.int32)
@@ -117,7 +128,8 @@ def sim_pairs(values, similarity_fn):
         # filter is the startup bottleneck at V ~ 10^5.
         if route == "gpu":
             row_ptr, col, expsim = _C.sim_pairs_gpu(
-                torch.from_numpy(buf).cuda(), torch.from_numpy(lens).cuda(), thr, msim
+                torch.from_numpy(buf).cuda(), torch.from_numpy(lens).cuda(), thr, msim,
+                transpositions,
             )
             # atomically-filled rows are unordered; sort within rows by col
             V = len(values)
@@ -133,7 +145,7 @@ def sim_pairs(values, similarity_fn):
                 expsim[order].cpu().numpy().astype(np.float64),
             )
         row_ptr, col, expsim = _C.sim_pairs_cpu(
-            torch.from_numpy(buf), torch.from_numpy(lens), thr, msim
+            torch.from_numpy(buf), torch.from_numpy(lens), thr, msim, transpositions
         )
         return SimIndexCSR(row_ptr.numpy().astype(np.int64), col.numpy(), expsim.numpy())
 

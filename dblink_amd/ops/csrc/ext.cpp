@@ -61,7 +61,8 @@ std::tuple<torch::Tensor, torch::Tensor> value_update_cpu(
 
 // sim_pairs_cpu.cpp
 std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim);
+                                         double threshold, double max_sim,
+                                         bool transpositions);
 
 // kernels.hip
 void link_update(torch::Tensor rec_values, torch::Tensor rec_dist,
@@ -172,7 +173,8 @@ void kd_descent(torch::Tensor ent_values, torch::Tensor node_kind,
                 torch::Tensor node_attr, torch::Tensor node_a, torch::Tensor node_b,
                 torch::Tensor rset, torch::Tensor ent_part_out);
 std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim);
+                                         double threshold, double max_sim,
+                                         bool transpositions);
 
 }  // namespace dblink
 
@@ -197,9 +199,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("summary_cpu", &dblink::summary_cpu,
         "summary reduction: loglik + isolates + distortion counts (OpenMP)");
   m.def("sim_pairs_cpu", &dblink::sim_pairs_cpu,
-        "banded Levenshtein sim-pair sweep (CPU/OpenMP)");
+        "banded Levenshtein / OSA sim-pair sweep (CPU/OpenMP)",
+        py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
+        py::arg("transpositions") = false);
   m.def("sim_pairs_gpu", &dblink::sim_pairs_gpu,
-        "banded Levenshtein sim-pair sweep (gfx950)");
+        "banded Levenshtein / OSA sim-pair sweep (gfx950)",
+        py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
+        py::arg("transpositions") = false);
   m.def("link_update", &dblink::link_update, "K3/K4/K5 fused link update");
   m.def("link_update_dense", &dblink::link_update_dense,
         "dense link update (PCG-II / Gibbs-Sequential)");

@@ -12,7 +12,7 @@
 //              build_ekeys_stable (+ rocprim radix sort), classify_modes
 //   --     mfma_score / scalar_score — matrix-core scoring experiment
 //   K9     kd_descent_kernel — flat KD-tree partition reassignment
-//   K1     sim_pairs_kernel — bit-parallel Levenshtein domain sweep
+//   K1     sim_pairs_kernel — bit-parallel Levenshtein / OSA domain sweep
 //
 // Wave kernels give one wave (64 lanes) a record or an (entity, attribute)
 // pair, 4 waves per block; thread kernels give one lane an item. All
@@ -2264,7 +2264,7 @@ __global__ void kd_descent_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// K1 (GPU): banded Levenshtein sim-pair sweep over a value domain
+// K1 (GPU): banded Levenshtein / OSA sim-pair sweep over a value domain
 // ---------------------------------------------------------------------------
 
 // One WAVE per value i: the wave builds a Myers bit-parallel Peq table for
@@ -2356,29 +2356,53 @@ struct SimPeq<uint16_t, W> {
 // bitwise except the add, which carries word to word, and the Ph/Mh left
 // shifts, which carry their top bit (Ph's low word shifts in 1). The caller
 // guarantees (m-1)/64 == W-1, so the score bit sits in the last word.
-template <typename Sym, int W>
+//
+// TRANSPOSE adds the restricted Damerau-Levenshtein (optimal string
+// alignment) term: an adjacent swap costs 1. Pattern position p may take a
+// diagonal-zero through a transposition at text position j when p matches
+// text j-1 (Eqprev), p-1 matches text j (Eq shifted up one, carrying across
+// words) and the cell two back on the diagonal was no diagonal-zero
+// (~D0prev). D0prev and Eqprev are the previous text position's D0 and Eq,
+// kept in registers per lane, and are 0 before the first character. The
+// term is OR-ed into Xh and Xv before Ph/Mh/Pv/Mv are formed; without
+// TRANSPOSE none of it is compiled.
+template <typename Sym, int W, bool TRANSPOSE>
 __device__ int myers_distance(const SimPeq<Sym, W>& peq, int m, const Sym* b, int lb) {
   if (m == 0) return lb;
   int score = m;
   unsigned long long Pv[W], Mv[W];
+  unsigned long long D0prev[W], Eqprev[W];  // TRANSPOSE only
 #pragma unroll
   for (int w = 0; w < W; ++w) {
     Pv[w] = ~0ull;
     Mv[w] = 0ull;
+    D0prev[w] = 0ull;
+    Eqprev[w] = 0ull;
   }
   const unsigned long long last = 1ull << ((m - 1) & 63);
   for (int j = 0; j < lb; ++j) {
     unsigned long long Eq[W];
     peq.lookup(b[j], Eq);
-    unsigned long long add_c = 0ull, ph_c = 1ull, mh_c = 0ull;
+    unsigned long long add_c = 0ull, ph_c = 1ull, mh_c = 0ull, tr_c = 0ull;
 #pragma unroll
     for (int w = 0; w < W; ++w) {
-      const unsigned long long Xv = Eq[w] | Mv[w];
+      unsigned long long Xv = Eq[w] | Mv[w];
       const unsigned long long t = Eq[w] & Pv[w];
       const unsigned long long s1 = t + Pv[w];
       const unsigned long long s2 = s1 + add_c;
       add_c = (unsigned long long)(s1 < t) | (unsigned long long)(s2 < s1);
-      const unsigned long long Xh = (s2 ^ Pv[w]) | Eq[w];
+      unsigned long long Xh = (s2 ^ Pv[w]) | Eq[w];
+      if constexpr (TRANSPOSE) {
+        // x's top bit carries into word w+1; it is taken from this word's
+        // previous-column D0 before that is overwritten below
+        const unsigned long long x = ~D0prev[w] & Eq[w];
+        const unsigned long long TR = ((x << 1) | tr_c) & Eqprev[w];
+        tr_c = x >> 63;
+        Xh |= TR;
+        Xv |= TR;
+        D0prev[w] = Xh | Mv[w];
+        Eqprev[w] = Eq[w];
+      }
       unsigned long long Ph = Mv[w] | ~(Xh | Pv[w]);
       unsigned long long Mh = Pv[w] & Xh;
       if (w == W - 1) {
@@ -2397,7 +2421,7 @@ __device__ int myers_distance(const SimPeq<Sym, W>& peq, int m, const Sym* b, in
   return score;
 }
 
-template <typename Sym, int W, int WAVES>
+template <typename Sym, int W, int WAVES, bool TRANSPOSE>
 __global__ void __launch_bounds__(WAVES * WAVE) sim_pairs_kernel(
     const Sym* __restrict__ strs,      // [V, max_len]
     const int32_t* __restrict__ lens,  // [V]
@@ -2454,7 +2478,8 @@ __global__ void __launch_bounds__(WAVES * WAVE) sim_pairs_kernel(
       unit = 1.0f;
     } else {
       if ((float)abs(la - lb) >= band * (float)tot) continue;
-      const int d = myers_distance<Sym, W>(peq, la, strs + (int64_t)j * max_len, lb);
+      const int d =
+          myers_distance<Sym, W, TRANSPOSE>(peq, la, strs + (int64_t)j * max_len, lb);
       unit = 1.0f - 2.0f * (float)d / ((float)tot + (float)d);
     }
     const float trans = scale * (max_sim * unit - threshold);
@@ -3104,6 +3129,7 @@ struct SimSweep {
   const int64_t* len_ptr;
   int max_len;
   float threshold, max_sim;
+  bool transpositions;  // OSA instead of Levenshtein
   int64_t* row_counts;
   int32_t* out_col;
   float* out_expsim;
@@ -3115,7 +3141,9 @@ template <typename Sym, int W, int WAVES>
 static void launch_sim_class(const SimSweep& s, int64_t row_begin, int64_t row_end) {
   if (row_end <= row_begin) return;
   dim3 grid((unsigned)wave_grid(row_end - row_begin, WAVES));
-  hipLaunchKernelGGL((sim_pairs_kernel<Sym, W, WAVES>), grid, dim3(WAVES * WAVE), 0,
+  const auto kernel = s.transpositions ? sim_pairs_kernel<Sym, W, WAVES, true>
+                                       : sim_pairs_kernel<Sym, W, WAVES, false>;
+  hipLaunchKernelGGL(kernel, grid, dim3(WAVES * WAVE), 0,
                      at::cuda::getCurrentCUDAStream(),
                      static_cast<const Sym*>(s.strs), s.lens, s.len_order, s.len_ptr,
                      row_begin, row_end, s.max_len, s.threshold, s.max_sim,
@@ -3134,7 +3162,8 @@ static void launch_sim_sweep(const SimSweep& s, const int64_t (&class_ptr)[5]) {
 }
 
 std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim) {
+                                         double threshold, double max_sim,
+                                         bool transpositions) {
   CHECK_GPU(strs);
   CHECK_GPU(lens);
   TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous(), "strs must be a contiguous [V, stride] tensor");
@@ -3174,6 +3203,7 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
   s.max_len = max_len;
   s.threshold = (float)threshold;
   s.max_sim = (float)max_sim;
+  s.transpositions = transpositions;
   auto sweep = [&]() {
     if (wide) launch_sim_sweep<uint16_t>(s, class_ptr);
     else launch_sim_sweep<uint8_t>(s, class_ptr);

@@ -1,4 +1,5 @@
-// CPU (OpenMP) banded Levenshtein sim-pair sweep over an attribute domain.
+// CPU (OpenMP) banded edit-distance (Levenshtein or OSA) sim-pair sweep over
+// an attribute domain.
 //
 // Replaces the reference's Spark cartesian V x V sweep
 // (AttributeIndex.scala:219-231) with a threshold-pruned exact pass:
@@ -49,7 +50,54 @@ static int levenshtein_capped(const Sym* a, int la, const Sym* b, int lb,
   return prev[lb];
 }
 
+// Restricted Damerau-Levenshtein (optimal string alignment): the recurrence
+// above plus D[i-2][j-2] + 1 where the last two symbols of both prefixes are
+// swapped, on three rolling rows of lb + 1 cells.
+//
+// The single-row early exit stays valid. D is 1-Lipschitz along a row (the
+// induction on i goes through with the transposition term), so if every cell
+// of row i exceeds `band`, every cell of row i-1 is at least `band`: a cell
+// of row i-1 below `band` would put its lower neighbour at or below `band`.
+// A transposition into row i+1 reads row i-1 and so yields at least
+// band + 1, like the three Levenshtein terms reading row i; every later row
+// therefore exceeds `band` too.
 template <typename Sym>
+static int osa_capped(const Sym* a, int la, const Sym* b, int lb, int band,
+                      int* scratch) {
+  if (la == 0) return lb;
+  if (lb == 0) return la;
+  int* prev2 = scratch + 2 * (lb + 1);  // row i-2, first read at i == 2
+  int* prev = scratch;
+  int* cur = scratch + lb + 1;
+  for (int j = 0; j <= lb; ++j) prev[j] = j;
+  for (int i = 1; i <= la; ++i) {
+    cur[0] = i;
+    int row_min = i;
+    const Sym ca = a[i - 1];
+    for (int j = 1; j <= lb; ++j) {
+      const int cost = (ca == b[j - 1]) ? 0 : 1;
+      int m = prev[j - 1] + cost;
+      const int del = cur[j - 1] + 1;
+      const int ins = prev[j] + 1;
+      if (del < m) m = del;
+      if (ins < m) m = ins;
+      if (i > 1 && j > 1 && ca == b[j - 2] && a[i - 2] == b[j - 1]) {
+        const int tr = prev2[j - 2] + 1;
+        if (tr < m) m = tr;
+      }
+      cur[j] = m;
+      if (m < row_min) row_min = m;
+    }
+    if (row_min > band) return band + 1;
+    int* t = prev2;
+    prev2 = prev;
+    prev = cur;
+    cur = t;
+  }
+  return prev[lb];
+}
+
+template <typename Sym, bool TRANSPOSE>
 static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::Tensor lens,
                                                      double threshold, double max_sim) {
   const int64_t V = strs.size(0);
@@ -66,7 +114,7 @@ static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::
   for (int64_t i = 0; i < V; ++i) {
     const Sym* a = S + i * max_len;
     const int la = L[i];
-    std::vector<int> scratch(2 * (max_len + 1));
+    std::vector<int> scratch((TRANSPOSE ? 3 : 2) * (max_len + 1));
     for (int64_t j = 0; j < V; ++j) {
       const int lb = L[j];
       const int tot = la + lb;
@@ -78,8 +126,9 @@ static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::
         const double dmax_f = tot * (1.0 - u0) / (1.0 + u0);
         const int band = (int)std::ceil(dmax_f);
         if (std::abs(la - lb) >= dmax_f) continue;
-        const int d = levenshtein_capped(a, la, S + j * max_len, lb, band,
-                                         scratch.data());
+        const int d = TRANSPOSE
+            ? osa_capped(a, la, S + j * max_len, lb, band, scratch.data())
+            : levenshtein_capped(a, la, S + j * max_len, lb, band, scratch.data());
         if (d > band) continue;
         unit = 1.0 - 2.0 * (double)d / ((double)tot + d);
       }
@@ -112,17 +161,23 @@ static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::
 }
 
 // strs: [V, stride] uint8 symbols, or 16-bit symbol ids in int16 storage
-// (read as uint16_t); id 0 pads either.
+// (read as uint16_t); id 0 pads either. `transpositions` selects the
+// restricted Damerau-Levenshtein (OSA) distance instead of Levenshtein.
 std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim) {
+                                         double threshold, double max_sim,
+                                         bool transpositions) {
   TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous() && !strs.is_cuda());
   TORCH_CHECK(lens.dtype() == torch::kInt32 && lens.is_contiguous() &&
               lens.numel() == strs.size(0));
   if (strs.scalar_type() == torch::kUInt8)
-    return sim_pairs_cpu_impl<uint8_t>(strs, lens, threshold, max_sim);
+    return transpositions
+        ? sim_pairs_cpu_impl<uint8_t, true>(strs, lens, threshold, max_sim)
+        : sim_pairs_cpu_impl<uint8_t, false>(strs, lens, threshold, max_sim);
   TORCH_CHECK(strs.scalar_type() == torch::kInt16 || strs.scalar_type() == torch::kUInt16,
               "strs must hold uint8 symbols or 16-bit symbol ids (int16 storage)");
-  return sim_pairs_cpu_impl<uint16_t>(strs, lens, threshold, max_sim);
+  return transpositions
+      ? sim_pairs_cpu_impl<uint16_t, true>(strs, lens, threshold, max_sim)
+      : sim_pairs_cpu_impl<uint16_t, false>(strs, lens, threshold, max_sim);
 }
 
 }  // namespace dblink

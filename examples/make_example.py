@@ -17,12 +17,18 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dblink_amd.utils.synthdata import write_csv
 
+# --similarity -> (config key, similarity function) of the string attributes
+SIMILARITY = {
+    "levenshtein": ("levSimFn", "LevenshteinSimilarityFn"),
+    "damerau": ("damSimFn", "DamerauLevenshteinSimilarityFn"),
+}
+
 CONF = """dblink : {{
     lowDistortion : {{alpha : {alpha}, beta : {beta}}}
 
     constSimFn : {{ name : "ConstantSimilarityFn" }}
-    levSimFn : {{
-        name : "LevenshteinSimilarityFn",
+    {sim_key} : {{
+        name : "{sim_name}",
         parameters : {{ threshold : 7.0, maxSimilarity : 10.0 }}
     }}
 
@@ -35,8 +41,8 @@ CONF = """dblink : {{
             {{name : "by", similarityFunction : ${{dblink.constSimFn}}, distortionPrior : ${{dblink.lowDistortion}}}},
             {{name : "bm", similarityFunction : ${{dblink.constSimFn}}, distortionPrior : ${{dblink.lowDistortion}}}},
             {{name : "bd", similarityFunction : ${{dblink.constSimFn}}, distortionPrior : ${{dblink.lowDistortion}}}},
-            {{name : "fname_c1", similarityFunction : ${{dblink.levSimFn}}, distortionPrior : ${{dblink.lowDistortion}}}},
-            {{name : "lname_c1", similarityFunction : ${{dblink.levSimFn}}, distortionPrior : ${{dblink.lowDistortion}}}}
+            {{name : "fname_c1", similarityFunction : ${{dblink.{sim_key}}}, distortionPrior : ${{dblink.lowDistortion}}}},
+            {{name : "lname_c1", similarityFunction : ${{dblink.{sim_key}}}, distortionPrior : ${{dblink.lowDistortion}}}}
         ]
     }}
 
@@ -82,6 +88,9 @@ def main():
     ap.add_argument("--files", type=int, default=1,
                     help="spread records over N source files (record linkage "
                          "with per-file distortion probabilities)")
+    ap.add_argument("--similarity", choices=sorted(SIMILARITY), default="levenshtein",
+                    help="similarity function of the name attributes; damerau "
+                         "counts an adjacent swap as one edit")
     args = ap.parse_args()
 
     os.makedirs(args.out, exist_ok=True)
@@ -94,7 +103,9 @@ def main():
     # RLdata10000.conf Beta(10, 1000)): a weak prior at large n lets the
     # chain drift to a high-distortion mode
     alpha, beta = (10.0, 1000.0) if args.records >= 5000 else (0.5, 50.0)
-    conf = CONF.format(out=args.out, levels=args.levels, part_attrs=part_attrs,
+    sim_key, sim_name = SIMILARITY[args.similarity]
+    conf = CONF.format(sim_key=sim_key, sim_name=sim_name,
+                       out=args.out, levels=args.levels, part_attrs=part_attrs,
                        samples=args.samples, burnin=args.burnin, thin=args.thin,
                        file_id_line=file_id_line, alpha=alpha, beta=beta,
                        cutoff=args.burnin + (args.samples * args.thin) // 2)

@@ -3,6 +3,7 @@
 
     python scripts/sim_sweep_bench.py [--v 20000] [--repeats 5]
                                       [--parent-ext /path/to/parent/_C*.so]
+                                      [--metric {levenshtein,osa}]
 
 Three seeded domains of V values, each built as clusters of mutated copies so
 that the index is not empty:
@@ -17,7 +18,10 @@ that the index is not empty:
 
 Every timed step runs in a child process of its own under ``timeout``; the
 driver stops at the first child that fails. The CPU pass uses the OpenMP
-thread count of the environment (OMP_NUM_THREADS). Prints one JSON document.
+thread count of the environment (OMP_NUM_THREADS). ``--metric osa`` times the
+transposition-aware sweeps instead (both the GPU and the CPU pass); a
+``--parent-ext`` build older than that metric can only be compared under the
+default, ``levenshtein``. Prints one JSON document.
 """
 
 import argparse
@@ -100,15 +104,18 @@ def worker(args):
     if buf.dtype == np.uint16:
         buf = buf.view(np.int16)
     tb, tl = torch.from_numpy(buf), torch.from_numpy(lens)
-    out = {"case": args.case, "kind": args.kind, "V": args.v, "ext": args.ext}
+    out = {"case": args.case, "kind": args.kind, "V": args.v, "ext": args.ext,
+           "metric": args.metric}
+    # the default keeps the four-argument call an older extension understands
+    extra = (True,) if args.metric == "osa" else ()
     if args.kind == "gpu":
         assert torch.cuda.is_available(), "the GPU timing needs a GPU"
         tb, tl = tb.cuda(), tl.cuda()
-        run = lambda: C.sim_pairs_gpu(tb, tl, THR, MSIM)  # noqa: E731
+        run = lambda: C.sim_pairs_gpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
         sync = torch.cuda.synchronize
     else:
         out["threads"] = torch.get_num_threads()
-        run = lambda: C.sim_pairs_cpu(tb, tl, THR, MSIM)  # noqa: E731
+        run = lambda: C.sim_pairs_cpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
         sync = lambda: None  # noqa: E731
     for _ in range(args.warmup):
         run()
@@ -126,10 +133,10 @@ def worker(args):
     print("RESULT " + json.dumps(out), flush=True)
 
 
-def spawn(ext, case, kind, v, repeats, warmup, limit):
+def spawn(ext, case, kind, v, repeats, warmup, limit, metric="levenshtein"):
     cmd = ["timeout", "-k", "10", str(limit), sys.executable, os.path.abspath(__file__),
            "--worker", "--ext", ext, "--case", case, "--kind", kind, "--v", str(v),
-           "--repeats", str(repeats), "--warmup", str(warmup)]
+           "--repeats", str(repeats), "--warmup", str(warmup), "--metric", metric]
     p = subprocess.run(cmd, capture_output=True, text=True)
     if p.returncode != 0:
         sys.stderr.write(p.stdout + p.stderr)
@@ -158,6 +165,10 @@ def main():
     ap.add_argument("--timeout", type=int, default=390, help="seconds per child step")
     ap.add_argument("--ext", default=None, help="extension to time (default: this tree's)")
     ap.add_argument("--parent-ext", default=None, help="parent commit's built extension")
+    ap.add_argument("--metric", choices=["levenshtein", "osa"], default="levenshtein",
+                    help="edit distance of both sweeps (osa: adjacent swaps cost 1)")
+    ap.add_argument("--short-cpu", action="store_true",
+                    help="also run the CPU pass on the short domain and compare nnz")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--case", default="short", help=argparse.SUPPRESS)
     ap.add_argument("--kind", default="gpu", help=argparse.SUPPRESS)
@@ -167,16 +178,17 @@ def main():
 
     ext = args.ext or sorted(glob.glob(os.path.join(ROOT, "dblink_amd", "_C*.so")))[0]
     cases = args.cases.split(",")
-    report = {"V": args.v, "threshold": THR, "max_similarity": MSIM}
+    report = {"V": args.v, "threshold": THR, "max_similarity": MSIM, "metric": args.metric}
     if "short" in cases:
         new, parent, digests = [], [], set()
         for _ in range(args.rounds if args.parent_ext else 1):
             if args.parent_ext:
                 r = spawn(args.parent_ext, "short", "gpu", args.v, args.repeats, args.warmup,
-                          args.timeout)
+                          args.timeout, args.metric)
                 parent += r["seconds"]
                 digests.add(r["digest"])
-            r = spawn(ext, "short", "gpu", args.v, args.repeats, args.warmup, args.timeout)
+            r = spawn(ext, "short", "gpu", args.v, args.repeats, args.warmup, args.timeout,
+                      args.metric)
             new += r["seconds"]
             digests.add(r["digest"])
         report["short"] = {"gpu": stats(new), "nnz": r["nnz"]}
@@ -187,18 +199,25 @@ def main():
             report["short"]["median_over_parent"] = report["short"]["gpu"]["median_s"] / sp["median_s"]
             report["short"]["within_parent_spread"] = (
                 report["short"]["gpu"]["median_s"] - sp["median_s"] <= sp["max_s"] - sp["min_s"])
+        if args.short_cpu:
+            c = spawn(ext, "short", "cpu", args.v, args.cpu_repeats, 0, args.timeout, args.metric)
+            report["short"]["vs_cpu"] = {
+                "V": args.v, "cpu": stats(c["seconds"]), "cpu_threads": c["threads"],
+                "same_nnz": r["nnz"] == c["nnz"]}
         print(json.dumps({"short": report["short"]}), flush=True)
     for case in ("long", "wide"):
         if case not in cases:
             continue
-        g = spawn(ext, case, "gpu", args.v, args.repeats, args.warmup, args.timeout)
+        g = spawn(ext, case, "gpu", args.v, args.repeats, args.warmup, args.timeout,
+                  args.metric)
         report[case] = {"gpu": stats(g["seconds"]), "nnz": g["nnz"]}
         # the CPU pass is quadratic in V and, on long values, in the length:
         # the pair is timed on identical buffers at a V the CPU finishes
         v = min(args.v, args.long_cpu_v) if case == "long" else args.v
         if v != args.v:
-            g = spawn(ext, case, "gpu", v, args.repeats, args.warmup, args.timeout)
-        c = spawn(ext, case, "cpu", v, args.cpu_repeats, 0, args.timeout)
+            g = spawn(ext, case, "gpu", v, args.repeats, args.warmup, args.timeout,
+                      args.metric)
+        c = spawn(ext, case, "cpu", v, args.cpu_repeats, 0, args.timeout, args.metric)
         report[case]["vs_cpu"] = {
             "V": v, "gpu": stats(g["seconds"]), "cpu": stats(c["seconds"]),
             "cpu_threads": c["threads"], "same_nnz": g["nnz"] == c["nnz"],
