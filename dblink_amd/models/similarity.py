@@ -12,6 +12,9 @@ Semantics match the reference (``SimilarityFn.scala:25-107``):
 - ``DamerauLevenshteinSimilarityFn(threshold, maxSimilarity)``: the same with
   ``d`` the restricted Damerau-Levenshtein (optimal string alignment)
   distance, which counts an adjacent swap as one edit. Not in the reference.
+- ``JaroSimilarityFn(threshold, maxSimilarity, prefixScale)``: the same
+  truncation and scaling over the Jaro similarity with the Winkler prefix
+  boost (``jaro_winkler``) as ``unit``. Not in the reference.
 
 These host implementations are the *oracle*; the batched V x V domain sweep
 used to build the attribute index runs in the native extension
@@ -24,7 +27,7 @@ from __future__ import annotations
 class SimilarityFn:
     is_constant = False
     # which native sweep metric (``dblink_amd.ops.sim_pairs``) computes this
-    # function: "levenshtein", "osa", or None for the pure-Python pass
+    # function: "levenshtein", "osa", "jaro", or None for the pure-Python pass
     native_metric = None
 
     def similarity(self, a: str, b: str) -> float:
@@ -99,16 +102,73 @@ def osa_distance(a: str, b: str) -> int:
     return prev[lb]
 
 
-class _EditSimilarityFn(SimilarityFn):
-    """Truncated, scaled normalized similarity over an integer edit distance.
+def jaro_parts(a: str, b: str):
+    """``(m, t)`` of the Jaro similarity: matches and transpositions.
 
-    Subclasses set ``_distance`` (the metric), ``_name`` (the config name)
-    and ``native_metric``.
+    Window ``r = max(max(|a|, |b|) // 2 - 1, 0)``. Greedy: each ``a[i]`` in
+    order takes the first unmatched ``j`` in ``[i-r, i+r]`` with
+    ``b[j] == a[i]``. ``t`` is half the number of positions at which the
+    matched characters of ``a`` and of ``b``, each in its own order, differ.
+    """
+    la, lb = len(a), len(b)
+    r = max(max(la, lb) // 2 - 1, 0)
+    taken = [False] * lb
+    matched_a = []
+    for i, ch in enumerate(a):
+        for j in range(max(i - r, 0), min(i + r + 1, lb)):
+            if not taken[j] and b[j] == ch:
+                taken[j] = True
+                matched_a.append(ch)
+                break
+    matched_b = [b[j] for j in range(lb) if taken[j]]
+    half = sum(1 for x, y in zip(matched_a, matched_b) if x != y)
+    return len(matched_a), half // 2
+
+
+def jaro_boost_gate(m: int, t: int, la: int, lb: int) -> bool:
+    """``jaro > 0.7`` decided in exact integers (needs ``m > 0``)."""
+    return 10 * (m * m * (la + lb) + (m - t) * la * lb) > 21 * m * la * lb
+
+
+def jaro(a: str, b: str) -> float:
+    """Jaro similarity in [0, 1]; 1.0 when both strings are empty."""
+    la, lb = len(a), len(b)
+    if la == 0 and lb == 0:
+        return 1.0
+    m, t = jaro_parts(a, b)
+    if m == 0:
+        return 0.0
+    return (m / la + m / lb + (m - t) / m) / 3.0
+
+
+def jaro_winkler(a: str, b: str, prefix_scale: float = 0.1) -> float:
+    """Jaro similarity with the Winkler boost ``l * p * (1 - jaro)`` for a
+    common prefix of ``l <= 4`` characters, applied only when ``jaro > 0.7``
+    (``jaro_boost_gate``)."""
+    la, lb = len(a), len(b)
+    if la == 0 and lb == 0:
+        return 1.0
+    m, t = jaro_parts(a, b)
+    if m == 0:
+        return 0.0
+    j = (m / la + m / lb + (m - t) / m) / 3.0
+    if not jaro_boost_gate(m, t, la, lb):
+        return j
+    l = 0
+    while l < min(4, la, lb) and a[l] == b[l]:
+        l += 1
+    return j + l * prefix_scale * (1.0 - j)
+
+
+class _ScaledSimilarityFn(SimilarityFn):
+    """Truncated, scaled similarity over a unit similarity in [0, 1]::
+
+        sim(a,b) = max(0, t * (S_max * unit(a,b) - thr)),  t = S_max/(S_max-thr)
+
+    Subclasses define ``unit_similarity``.
     """
 
     is_constant = False
-    _distance = None
-    _name = None
 
     def __init__(self, threshold: float = 7.0, max_similarity: float = 10.0):
         if max_similarity <= 0.0:
@@ -120,15 +180,29 @@ class _EditSimilarityFn(SimilarityFn):
         self.trans_factor = max_similarity / (max_similarity - threshold)
 
     def unit_similarity(self, a: str, b: str) -> float:
+        raise NotImplementedError
+
+    def similarity(self, a: str, b: str) -> float:
+        s = self.trans_factor * (self.max_similarity * self.unit_similarity(a, b) - self.threshold)
+        return s if s > 0.0 else 0.0
+
+
+class _EditSimilarityFn(_ScaledSimilarityFn):
+    """Truncated, scaled normalized similarity over an integer edit distance.
+
+    Subclasses set ``_distance`` (the metric), ``_name`` (the config name)
+    and ``native_metric``.
+    """
+
+    _distance = None
+    _name = None
+
+    def unit_similarity(self, a: str, b: str) -> float:
         total = len(a) + len(b)
         if total == 0:
             return 1.0
         d = type(self)._distance(a, b)
         return 1.0 - 2.0 * d / (total + d)
-
-    def similarity(self, a: str, b: str) -> float:
-        s = self.trans_factor * (self.max_similarity * self.unit_similarity(a, b) - self.threshold)
-        return s if s > 0.0 else 0.0
 
     def mk_string(self) -> str:
         return f"{self._name}(threshold={self.threshold}, maxSimilarity={self.max_similarity})"
@@ -164,6 +238,43 @@ class DamerauLevenshteinSimilarityFn(_EditSimilarityFn):
     _name = "DamerauLevenshteinSimilarityFn"
 
 
+class JaroSimilarityFn(_ScaledSimilarityFn):
+    """Truncated, scaled Jaro similarity with the Winkler prefix boost.
+
+    ``unit`` is ``jaro_winkler(a, b, prefix_scale)``; ``prefix_scale = 0``
+    gives plain Jaro. The config name is ``JaroSimilarityFn``: the boost is a
+    parameter (``prefixScale``), not part of the name.
+    """
+
+    native_metric = "jaro"
+    _name = "JaroSimilarityFn"
+
+    def __init__(self, threshold: float = 7.0, max_similarity: float = 10.0,
+                 prefix_scale: float = 0.1):
+        super().__init__(threshold, max_similarity)
+        if not (0.0 <= prefix_scale <= 0.25):
+            raise ValueError("`prefixScale` must be in [0, 0.25]")
+        self.prefix_scale = float(prefix_scale)
+
+    def unit_similarity(self, a: str, b: str) -> float:
+        return jaro_winkler(a, b, self.prefix_scale)
+
+    def mk_string(self) -> str:
+        return (f"{self._name}(threshold={self.threshold}, "
+                f"maxSimilarity={self.max_similarity}, prefixScale={self.prefix_scale})")
+
+    def __eq__(self, other):
+        return (
+            type(other) is type(self)
+            and other.threshold == self.threshold
+            and other.max_similarity == self.max_similarity
+            and other.prefix_scale == self.prefix_scale
+        )
+
+    def __hash__(self):
+        return hash((self._name, self.threshold, self.max_similarity, self.prefix_scale))
+
+
 _EDIT_FNS = {c._name: c for c in (LevenshteinSimilarityFn, DamerauLevenshteinSimilarityFn)}
 
 
@@ -176,5 +287,11 @@ def similarity_fn_from_config(cfg) -> SimilarityFn:
         return _EDIT_FNS[name](
             threshold=cfg.get_double("parameters.threshold"),
             max_similarity=cfg.get_double("parameters.maxSimilarity"),
+        )
+    if name == JaroSimilarityFn._name:
+        return JaroSimilarityFn(
+            threshold=cfg.get_double("parameters.threshold"),
+            max_similarity=cfg.get_double("parameters.maxSimilarity"),
+            prefix_scale=float(cfg.get_or("parameters.prefixScale", 0.1)),
         )
     raise ValueError(f"unsupported similarity function: {name!r}")

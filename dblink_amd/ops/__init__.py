@@ -40,7 +40,7 @@ def native():
     return _C
 
 
-SIM_GPU_MAX_LEN = 256  # sim_pairs_kernel: four 64-bit Myers words per pattern
+SIM_GPU_MAX_LEN = 256  # sim_pairs_kernel, jaro_pairs_kernel: four 64-bit words per pattern
 SIM_MAX_SYMBOLS = 65535  # 16-bit symbol ids, 0 reserved for padding
 
 
@@ -67,8 +67,9 @@ def sim_pairs(values, similarity_fn):
     Returns a ``SimIndexCSR``. Replaces the reference's Spark ``cartesian``
     V x V sweep (``AttributeIndex.scala:219-231``) with a length-pruned
     banded edit-distance pass. ``similarity_fn.native_metric`` selects the
-    metric of the native sweeps: ``"levenshtein"``, or ``"osa"`` (adjacent
-    transpositions at cost 1).
+    metric of the native sweeps: ``"levenshtein"``, ``"osa"`` (adjacent
+    transpositions at cost 1) or ``"jaro"`` (Jaro similarity with the Winkler
+    prefix boost, scaled by ``similarity_fn.prefix_scale``).
     """
     from ..models.attribute_index import SimIndexCSR, _python_sim_pairs
 
@@ -81,11 +82,15 @@ def sim_pairs(values, similarity_fn):
     metric = getattr(similarity_fn, "native_metric", None)
     if metric is None:
         return _python_sim_pairs(values, similarity_fn)
-    if metric not in ("levenshtein", "osa"):
+    if metric not in ("levenshtein", "osa", "jaro"):
         raise ValueError(f"unknown native similarity metric: {metric!r}")
-    transpositions = metric == "osa"
+    # (sweep name, last argument) of the metric's native entry points
+    if metric == "jaro":
+        sweep, sweep_arg = "jaro_pairs", float(similarity_fn.prefix_scale)
+    else:
+        sweep, sweep_arg = "sim_pairs", metric == "osa"
 
-    # Edit distance must be over CHARACTERS (the reference uses JVM strings,
+    # The similarity must be over CHARACTERS (the reference uses JVM strings,
     # SimilarityFn.scala:92-98). Encode through a per-domain character
     # vocabulary, one symbol id per character (0 pads), so symbol-level
     # distance == character-level: uint8 ids up to 255 distinct
@@ -94,7 +99,7 @@ def sim_pairs(values, similarity_fn):
     lens = np.array([len(v) for v in values], dtype=np.int32)
     maxlen = int(lens.max()) if len(lens) else 0
     cuda = False
-    if _C is not None and hasattr(_C, "sim_pairs_gpu"):
+    if _C is not None and hasattr(_C, sweep + "_gpu"):
         import torch
 
         cuda = torch.cuda.is_available()
@@ -108,7 +113,7 @@ def sim_pairs(values, similarity_fn):
             "pure-Python pass",
             len(charset), SIM_MAX_SYMBOLS,
         )
-    if route != "python" and _C is not None and hasattr(_C, "sim_pairs_cpu"):
+    if route != "python" and _C is not None and hasattr(_C, sweep + "_cpu"):
         import torch
 
         vocab = {ch: i + 1 for i, ch in enumerate(charset)}
@@ -127,9 +132,9 @@ def sim_pairs(values, similarity_fn):
         # cartesian analog, AttributeIndex.scala:222-231) — the quadratic pair
         # filter is the startup bottleneck at V ~ 10^5.
         if route == "gpu":
-            row_ptr, col, expsim = _C.sim_pairs_gpu(
+            row_ptr, col, expsim = getattr(_C, sweep + "_gpu")(
                 torch.from_numpy(buf).cuda(), torch.from_numpy(lens).cuda(), thr, msim,
-                transpositions,
+                sweep_arg,
             )
             # atomically-filled rows are unordered; sort within rows by col
             V = len(values)
@@ -144,8 +149,8 @@ def sim_pairs(values, similarity_fn):
                 col[order].cpu().numpy(),
                 expsim[order].cpu().numpy().astype(np.float64),
             )
-        row_ptr, col, expsim = _C.sim_pairs_cpu(
-            torch.from_numpy(buf), torch.from_numpy(lens), thr, msim, transpositions
+        row_ptr, col, expsim = getattr(_C, sweep + "_cpu")(
+            torch.from_numpy(buf), torch.from_numpy(lens), thr, msim, sweep_arg
         )
         return SimIndexCSR(row_ptr.numpy().astype(np.int64), col.numpy(), expsim.numpy())
 

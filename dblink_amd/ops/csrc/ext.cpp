@@ -63,6 +63,9 @@ std::tuple<torch::Tensor, torch::Tensor> value_update_cpu(
 std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
                                          double threshold, double max_sim,
                                          bool transpositions);
+std::vector<torch::Tensor> jaro_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
+                                          double threshold, double max_sim,
+                                          double prefix_scale);
 
 // kernels.hip
 void link_update(torch::Tensor rec_values, torch::Tensor rec_dist,
@@ -175,6 +178,9 @@ void kd_descent(torch::Tensor ent_values, torch::Tensor node_kind,
 std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
                                          double threshold, double max_sim,
                                          bool transpositions);
+std::vector<torch::Tensor> jaro_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
+                                          double threshold, double max_sim,
+                                          double prefix_scale);
 
 }  // namespace dblink
 
@@ -206,6 +212,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "banded Levenshtein / OSA sim-pair sweep (gfx950)",
         py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
         py::arg("transpositions") = false);
+  m.def("jaro_pairs_cpu", &dblink::jaro_pairs_cpu,
+        "Jaro sim-pair sweep with the Winkler prefix boost (CPU/OpenMP)",
+        py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
+        py::arg("prefix_scale"));
+  m.def("jaro_pairs_gpu", &dblink::jaro_pairs_gpu,
+        "Jaro sim-pair sweep with the Winkler prefix boost (gfx950)",
+        py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
+        py::arg("prefix_scale"));
   m.def("link_update", &dblink::link_update, "K3/K4/K5 fused link update");
   m.def("link_update_dense", &dblink::link_update_dense,
         "dense link update (PCG-II / Gibbs-Sequential)");

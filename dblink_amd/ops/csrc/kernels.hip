@@ -13,6 +13,7 @@
 //   --     mfma_score / scalar_score — matrix-core scoring experiment
 //   K9     kd_descent_kernel — flat KD-tree partition reassignment
 //   K1     sim_pairs_kernel — bit-parallel Levenshtein / OSA domain sweep
+//          jaro_pairs_kernel — bit-parallel Jaro(-Winkler) domain sweep
 //
 // Wave kernels give one wave (64 lanes) a record or an (entity, attribute)
 // pair, 4 waves per block; thread kernels give one lane an item. All
@@ -25,6 +26,7 @@
 #include <torch/extension.h>
 
 #include "common.h"
+#include "jaro.h"
 
 namespace dblink {
 
@@ -2499,6 +2501,168 @@ __global__ void __launch_bounds__(WAVES * WAVE) sim_pairs_kernel(
 }
 
 // ---------------------------------------------------------------------------
+// K1 (GPU): Jaro sim-pair sweep with the Winkler prefix boost
+// ---------------------------------------------------------------------------
+
+// Bits lo..hi of the 64*W-bit pattern that fall into word w (empty when
+// hi < lo). Every shift count stays within 0..63.
+__device__ __forceinline__ unsigned long long jaro_window_word(int lo, int hi, int w) {
+  int l = lo - 64 * w, h = hi - 64 * w;
+  if (h < 0 || l > 63 || h < l) return 0ull;
+  if (l < 0) l = 0;
+  if (h > 63) h = 63;
+  return (~0ull << l) & (~0ull >> (63 - h));
+}
+
+// Matches m and transpositions t of the pattern (masks in `peq`, length
+// la >= 1) against the text b (length lb >= 1), definition in jaro.h. The text
+// is the outer string of the greedy matching; m and t do not depend on which
+// string is the outer one (tests/test_similarity_jaro.py checks that).
+//
+// P_flag holds the matched pattern positions, T_flag the matched text
+// positions (a text has up to 256 symbols at any W). Text position j takes
+// the lowest free pattern position within [j-r, j+r] that holds its symbol.
+// The second loop pairs the matched text positions, ascending, with the
+// matched pattern positions, ascending: the two symbols agree exactly when
+// the text symbol's mask has that pattern bit. All array indices are
+// compile-time after unrolling, so the flags stay in registers.
+template <typename Sym, int W>
+__device__ void jaro_matches(const SimPeq<Sym, W>& peq, int la, const Sym* b, int lb,
+                             int* m_out, int* t_out) {
+  const int longer = la > lb ? la : lb;
+  const int r = longer / 2 - 1 > 0 ? longer / 2 - 1 : 0;
+  unsigned long long P_flag[W], T_flag[4];
+#pragma unroll
+  for (int w = 0; w < W; ++w) P_flag[w] = 0ull;
+#pragma unroll
+  for (int w = 0; w < 4; ++w) T_flag[w] = 0ull;
+  // text positions past la - 1 + r see an empty window
+  const int j_end = lb < la + r ? lb : la + r;
+  for (int j = 0; j < j_end; ++j) {
+    unsigned long long Eq[W];
+    peq.lookup(b[j], Eq);
+    const int lo = j - r > 0 ? j - r : 0;
+    const int hi = j + r < la - 1 ? j + r : la - 1;  // never a bit at or above la
+    bool taken = false;
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      const unsigned long long PM = Eq[w] & jaro_window_word(lo, hi, w) & ~P_flag[w];
+      const unsigned long long low = PM & (0ull - PM);
+      P_flag[w] |= taken ? 0ull : low;
+      taken = taken || PM != 0ull;
+    }
+    const unsigned long long tbit = taken ? 1ull << (j & 63) : 0ull;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) T_flag[w] |= (j >> 6) == w ? tbit : 0ull;
+  }
+  int m = 0;
+#pragma unroll
+  for (int w = 0; w < W; ++w) m += __popcll(P_flag[w]);
+  int half = 0;
+#pragma unroll
+  for (int tw = 0; tw < 4; ++tw) {
+    unsigned long long T = T_flag[tw];
+    while (T != 0ull) {
+      const int j = 64 * tw + __builtin_ctzll(T);
+      T &= T - 1ull;
+      unsigned long long Eq[W];
+      peq.lookup(b[j], Eq);
+      bool found = false, same = false;
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        const unsigned long long q = found ? 0ull : P_flag[w] & (0ull - P_flag[w]);
+        same = same || (Eq[w] & q) != 0ull;
+        P_flag[w] ^= q;
+        found = found || q != 0ull;
+      }
+      half += same ? 0 : 1;
+    }
+  }
+  *m_out = m;
+  *t_out = half >> 1;
+}
+
+// Launched like sim_pairs_kernel: one wave per row value of one length class,
+// the row's masks in LDS, lanes striding over the candidate window, a count
+// pass (fill == 0) and a fill pass. The score is formed in fp64 from the
+// integers (jaro_trans), so a pair enters the index here exactly when it does
+// in jaro_pairs_cpu; only exp() of the result is fp32.
+template <typename Sym, int W, int WAVES>
+__global__ void __launch_bounds__(WAVES * WAVE) jaro_pairs_kernel(
+    const Sym* __restrict__ strs,      // [V, max_len]
+    const int32_t* __restrict__ lens,  // [V]
+    const int32_t* __restrict__ len_order,  // [V] value ids sorted by length
+    const int64_t* __restrict__ len_ptr,    // [max_len + 2] bucket offsets by length
+    int64_t row_begin, int64_t row_end,     // this class's slice of len_order
+    int max_len, JaroScale sc,
+    int64_t* __restrict__ row_counts,  // [V] (pass 1 out) or row offsets (pass 2 in)
+    int32_t* __restrict__ out_col,     // pass 2
+    float* __restrict__ out_expsim,    // pass 2 (stores exp(sim))
+    int64_t* __restrict__ fill_pos,    // [V] atomic cursors (pass 2)
+    int fill) {
+  __shared__ unsigned long long peq_block[WAVES * SimPeq<Sym, W>::WORDS];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t r = row_end - 1 - ((int64_t)blockIdx.x * WAVES + wave);
+  if (r < row_begin) return;
+  const int i = len_order[r];
+  SimPeq<Sym, W> peq(peq_block + wave * SimPeq<Sym, W>::WORDS);
+  const int la = lens[i];
+  const Sym* a = strs + (int64_t)i * max_len;
+  peq.clear(lane);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+  for (int p = lane; p < la; p += WAVE) peq.insert(a[p], p);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_wave_barrier();
+
+  // Length window from jaro_length_prunes: unit can exceed u0 only when
+  // min/max of the two lengths exceeds q. One length of slack on either side
+  // covers the rounding of the products; the per-pair test below decides.
+  int lb_min = 0, lb_max = max_len;
+  const double boost = 4.0 * sc.prefix_scale;
+  if (boost < 1.0) {
+    const double q = 3.0 * (sc.u0 - boost) / (1.0 - boost) - 2.0;
+    if (q > 0.0) {
+      lb_min = (int)floor(q * (double)la) - 1;
+      const double top = ceil((double)la / q) + 1.0;
+      if (top < (double)max_len) lb_max = (int)top;
+    }
+  }
+  if (la == 0) { lb_min = 0; lb_max = 0; }  // an empty value scores with itself only
+  if (lb_min < 0) lb_min = 0;
+  if (lb_max > max_len) lb_max = max_len;
+  const int64_t j0 = len_ptr[lb_min], j1 = len_ptr[lb_max + 1];
+
+  int64_t n_hits = 0;
+  for (int64_t jj = j0 + lane; jj < j1; jj += WAVE) {
+    const int j = len_order[jj];
+    const int lb = lens[j];
+    if (jaro_length_prunes(sc, la, lb)) continue;
+    const Sym* b = strs + (int64_t)j * max_len;
+    int m = 0, t = 0;
+    if (la > 0 && lb > 0) jaro_matches<Sym, W>(peq, la, b, lb, &m, &t);
+    if (m == 0 && la + lb > 0) continue;  // unit 0
+    // 32-bit gate: lengths are at most SP_MAX_LEN
+    const double trans = jaro_trans<int>(sc, m, t, la, lb, jaro_common_prefix(a, la, b, lb));
+    // exp(trans) > 1 in fp64, the CPU sweep's criterion: 1 + x rounds above 1
+    // exactly when x > 2^-53
+    if (!(trans > 0x1p-53)) continue;
+    if (!fill) {
+      ++n_hits;
+    } else {
+      const int64_t pos = atomicAdd((unsigned long long*)&fill_pos[i], 1ull) + row_counts[i];
+      out_col[pos] = j;
+      out_expsim[pos] = __expf((float)trans);
+    }
+  }
+  if (!fill) {
+    double total = wave_sum((double)n_hits);
+    if (lane == 0) row_counts[i] = (int64_t)(total + 0.5);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
 
@@ -3121,15 +3285,13 @@ void kd_descent(
                      ent_part_out.data_ptr<int32_t>());
 }
 
-// One pass (count or fill) of the sweep's operands; shapes are on
-// sim_pairs_kernel's parameter list.
+// One pass (count or fill) of a K1 sweep's operands, whatever the metric;
+// shapes are on sim_pairs_kernel's parameter list.
 struct SimSweep {
   const void* strs;
   const int32_t *lens, *len_order;
   const int64_t* len_ptr;
   int max_len;
-  float threshold, max_sim;
-  bool transpositions;  // OSA instead of Levenshtein
   int64_t* row_counts;
   int32_t* out_col;
   float* out_expsim;
@@ -3137,33 +3299,55 @@ struct SimSweep {
   int fill;
 };
 
+// What a sweep scores with: launch_sim_class is overloaded on these.
+struct EditMetric {
+  float threshold, max_sim;
+  bool transpositions;  // OSA instead of Levenshtein
+};
+
 template <typename Sym, int W, int WAVES>
-static void launch_sim_class(const SimSweep& s, int64_t row_begin, int64_t row_end) {
+static void launch_sim_class(const SimSweep& s, const EditMetric& m, int64_t row_begin,
+                             int64_t row_end) {
   if (row_end <= row_begin) return;
   dim3 grid((unsigned)wave_grid(row_end - row_begin, WAVES));
-  const auto kernel = s.transpositions ? sim_pairs_kernel<Sym, W, WAVES, true>
+  const auto kernel = m.transpositions ? sim_pairs_kernel<Sym, W, WAVES, true>
                                        : sim_pairs_kernel<Sym, W, WAVES, false>;
   hipLaunchKernelGGL(kernel, grid, dim3(WAVES * WAVE), 0,
                      at::cuda::getCurrentCUDAStream(),
                      static_cast<const Sym*>(s.strs), s.lens, s.len_order, s.len_ptr,
-                     row_begin, row_end, s.max_len, s.threshold, s.max_sim,
+                     row_begin, row_end, s.max_len, m.threshold, m.max_sim,
+                     s.row_counts, s.out_col, s.out_expsim, s.fill_pos, s.fill);
+}
+
+template <typename Sym, int W, int WAVES>
+static void launch_sim_class(const SimSweep& s, const JaroScale& m, int64_t row_begin,
+                             int64_t row_end) {
+  if (row_end <= row_begin) return;
+  dim3 grid((unsigned)wave_grid(row_end - row_begin, WAVES));
+  hipLaunchKernelGGL((jaro_pairs_kernel<Sym, W, WAVES>), grid, dim3(WAVES * WAVE), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     static_cast<const Sym*>(s.strs), s.lens, s.len_order, s.len_ptr,
+                     row_begin, row_end, s.max_len, m,
                      s.row_counts, s.out_col, s.out_expsim, s.fill_pos, s.fill);
 }
 
 // One kernel instance per row-length class; class_ptr[k] is the first
 // len_order position whose length exceeds 64*k.
-template <typename Sym>
-static void launch_sim_sweep(const SimSweep& s, const int64_t (&class_ptr)[5]) {
+template <typename Sym, typename Metric>
+static void launch_sim_sweep(const SimSweep& s, const Metric& m, const int64_t (&class_ptr)[5]) {
   constexpr int WIDE = sizeof(Sym) == 1 ? SP_WAVES : SP_WAVES_WIDE;
-  launch_sim_class<Sym, 1, SP_WAVES>(s, class_ptr[0], class_ptr[1]);
-  launch_sim_class<Sym, 2, SP_WAVES>(s, class_ptr[1], class_ptr[2]);
-  launch_sim_class<Sym, 3, WIDE>(s, class_ptr[2], class_ptr[3]);
-  launch_sim_class<Sym, 4, WIDE>(s, class_ptr[3], class_ptr[4]);
+  launch_sim_class<Sym, 1, SP_WAVES>(s, m, class_ptr[0], class_ptr[1]);
+  launch_sim_class<Sym, 2, SP_WAVES>(s, m, class_ptr[1], class_ptr[2]);
+  launch_sim_class<Sym, 3, WIDE>(s, m, class_ptr[2], class_ptr[3]);
+  launch_sim_class<Sym, 4, WIDE>(s, m, class_ptr[3], class_ptr[4]);
 }
 
-std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
-                                         double threshold, double max_sim,
-                                         bool transpositions) {
+// The host side of a K1 sweep, shared by the metrics: operand checks, length
+// order and buckets, class boundaries, then a count pass, the CSR allocation
+// and a fill pass. `who` names the entry point in error messages.
+template <typename Metric>
+static std::vector<torch::Tensor> sim_sweep_gpu(torch::Tensor strs, torch::Tensor lens,
+                                                const Metric& metric, const char* who) {
   CHECK_GPU(strs);
   CHECK_GPU(lens);
   TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous(), "strs must be a contiguous [V, stride] tensor");
@@ -3174,7 +3358,7 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
               lens.numel() == strs.size(0), "lens must be a contiguous int32 [V] tensor");
   const int V = (int)strs.size(0);
   const int max_len = (int)strs.size(1);
-  TORCH_CHECK(max_len <= SP_MAX_LEN, "sim_pairs_gpu: row stride ", max_len,
+  TORCH_CHECK(max_len <= SP_MAX_LEN, who, ": row stride ", max_len,
               " exceeds the GPU sweep's limit of ", SP_MAX_LEN,
               " symbols per value (longer domains take the CPU pass)");
   auto opts_i64 = torch::TensorOptions().dtype(torch::kInt64).device(strs.device());
@@ -3201,12 +3385,9 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
   s.len_order = len_order.data_ptr<int32_t>();
   s.len_ptr = len_ptr.data_ptr<int64_t>();
   s.max_len = max_len;
-  s.threshold = (float)threshold;
-  s.max_sim = (float)max_sim;
-  s.transpositions = transpositions;
   auto sweep = [&]() {
-    if (wide) launch_sim_sweep<uint16_t>(s, class_ptr);
-    else launch_sim_sweep<uint8_t>(s, class_ptr);
+    if (wide) launch_sim_sweep<uint16_t>(s, metric, class_ptr);
+    else launch_sim_sweep<uint8_t>(s, metric, class_ptr);
   };
 
   auto row_counts = torch::zeros({V}, opts_i64);
@@ -3230,6 +3411,23 @@ std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
   s.fill = 1;
   sweep();
   return {row_ptr, col, expsim};
+}
+
+std::vector<torch::Tensor> sim_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
+                                         double threshold, double max_sim,
+                                         bool transpositions) {
+  const EditMetric metric{(float)threshold, (float)max_sim, transpositions};
+  return sim_sweep_gpu(strs, lens, metric, "sim_pairs_gpu");
+}
+
+// prefix_scale is Winkler's p (0 = plain Jaro); everything else as above.
+std::vector<torch::Tensor> jaro_pairs_gpu(torch::Tensor strs, torch::Tensor lens,
+                                          double threshold, double max_sim,
+                                          double prefix_scale) {
+  TORCH_CHECK(prefix_scale >= 0.0 && prefix_scale <= 0.25,
+              "prefix_scale must be in [0, 0.25]");
+  return sim_sweep_gpu(strs, lens, jaro_scale(threshold, max_sim, prefix_scale),
+                       "jaro_pairs_gpu");
 }
 
 }  // namespace dblink

@@ -7,6 +7,9 @@
 // d < (|a|+|b|) * (1-u0)/(1+u0), which bounds |len(a)-len(b)| and enables a
 // banded DP with early exit. Used at index-build time on the host; the GPU
 // variant lives in kernels.hip (sim_pairs_gpu).
+//
+// jaro_pairs_cpu is the same sweep over the Jaro similarity with the Winkler
+// prefix boost (GPU variant: jaro_pairs_gpu).
 
 #include <torch/extension.h>
 
@@ -14,6 +17,8 @@
 #include <cmath>
 #include <cstdint>
 #include <vector>
+
+#include "jaro.h"
 
 namespace dblink {
 
@@ -97,6 +102,26 @@ static int osa_capped(const Sym* a, int la, const Sym* b, int lb, int band,
   return prev[lb];
 }
 
+// Per-row hit lists to CSR (row_ptr int64, col int32, expsim fp32).
+static std::vector<torch::Tensor> rows_to_csr(const std::vector<std::vector<int32_t>>& cols,
+                                              const std::vector<std::vector<float>>& sims) {
+  const int64_t V = (int64_t)cols.size();
+  auto row_ptr = torch::zeros({V + 1}, torch::kInt64);
+  int64_t* rp = row_ptr.data_ptr<int64_t>();
+  for (int64_t i = 0; i < V; ++i) rp[i + 1] = rp[i] + (int64_t)cols[i].size();
+  const int64_t nnz = rp[V];
+  auto col = torch::empty({nnz}, torch::kInt32);
+  auto expsim = torch::empty({nnz}, torch::kFloat32);
+  int32_t* cp = col.data_ptr<int32_t>();
+  float* sp = expsim.data_ptr<float>();
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < V; ++i) {
+    std::copy(cols[i].begin(), cols[i].end(), cp + rp[i]);
+    std::copy(sims[i].begin(), sims[i].end(), sp + rp[i]);
+  }
+  return {row_ptr, col, expsim};
+}
+
 template <typename Sym, bool TRANSPOSE>
 static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::Tensor lens,
                                                      double threshold, double max_sim) {
@@ -144,20 +169,7 @@ static std::vector<torch::Tensor> sim_pairs_cpu_impl(torch::Tensor strs, torch::
     }
   }
 
-  auto row_ptr = torch::zeros({V + 1}, torch::kInt64);
-  int64_t* rp = row_ptr.data_ptr<int64_t>();
-  for (int64_t i = 0; i < V; ++i) rp[i + 1] = rp[i] + (int64_t)cols[i].size();
-  const int64_t nnz = rp[V];
-  auto col = torch::empty({nnz}, torch::kInt32);
-  auto expsim = torch::empty({nnz}, torch::kFloat32);
-  int32_t* cp = col.data_ptr<int32_t>();
-  float* sp = expsim.data_ptr<float>();
-#pragma omp parallel for schedule(static)
-  for (int64_t i = 0; i < V; ++i) {
-    std::copy(cols[i].begin(), cols[i].end(), cp + rp[i]);
-    std::copy(sims[i].begin(), sims[i].end(), sp + rp[i]);
-  }
-  return {row_ptr, col, expsim};
+  return rows_to_csr(cols, sims);
 }
 
 // strs: [V, stride] uint8 symbols, or 16-bit symbol ids in int16 storage
@@ -178,6 +190,60 @@ std::vector<torch::Tensor> sim_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
   return transpositions
       ? sim_pairs_cpu_impl<uint16_t, true>(strs, lens, threshold, max_sim)
       : sim_pairs_cpu_impl<uint16_t, false>(strs, lens, threshold, max_sim);
+}
+
+// Jaro similarity with the Winkler prefix boost (jaro.h) over every pair the
+// conservative length filter lets through; any value length.
+template <typename Sym>
+static std::vector<torch::Tensor> jaro_pairs_cpu_impl(torch::Tensor strs, torch::Tensor lens,
+                                                      const JaroScale& sc) {
+  const int64_t V = strs.size(0);
+  const int64_t max_len = strs.size(1);
+  const Sym* S = static_cast<const Sym*>(strs.data_ptr());
+  const int32_t* L = lens.data_ptr<int32_t>();
+
+  std::vector<std::vector<int32_t>> cols(V);
+  std::vector<std::vector<float>> sims(V);
+
+#pragma omp parallel for schedule(dynamic, 16)
+  for (int64_t i = 0; i < V; ++i) {
+    const Sym* a = S + i * max_len;
+    const int la = L[i];
+    std::vector<uint8_t> taken(max_len + 1);
+    std::vector<Sym> matched(max_len + 1);
+    for (int64_t j = 0; j < V; ++j) {
+      const int lb = L[j];
+      if (jaro_length_prunes(sc, la, lb)) continue;
+      const Sym* b = S + j * max_len;
+      int m = 0, t = 0;
+      if (la > 0 && lb > 0) jaro_parts_host(a, la, b, lb, taken.data(), matched.data(), &m, &t);
+      const int prefix = jaro_common_prefix(a, la, b, lb);
+      const double trans = jaro_trans<int64_t>(sc, m, t, la, lb, prefix);
+      const double es = std::exp(trans);  // inclusion as in sim_pairs_cpu_impl
+      if (es > 1.0) {
+        cols[i].push_back((int32_t)j);
+        sims[i].push_back((float)es);
+      }
+    }
+  }
+  return rows_to_csr(cols, sims);
+}
+
+// Same buffers as sim_pairs_cpu; prefix_scale is Winkler's p (0 = plain Jaro).
+std::vector<torch::Tensor> jaro_pairs_cpu(torch::Tensor strs, torch::Tensor lens,
+                                          double threshold, double max_sim,
+                                          double prefix_scale) {
+  TORCH_CHECK(strs.dim() == 2 && strs.is_contiguous() && !strs.is_cuda());
+  TORCH_CHECK(lens.dtype() == torch::kInt32 && lens.is_contiguous() &&
+              lens.numel() == strs.size(0));
+  TORCH_CHECK(prefix_scale >= 0.0 && prefix_scale <= 0.25,
+              "prefix_scale must be in [0, 0.25]");
+  const JaroScale sc = jaro_scale(threshold, max_sim, prefix_scale);
+  if (strs.scalar_type() == torch::kUInt8)
+    return jaro_pairs_cpu_impl<uint8_t>(strs, lens, sc);
+  TORCH_CHECK(strs.scalar_type() == torch::kInt16 || strs.scalar_type() == torch::kUInt16,
+              "strs must hold uint8 symbols or 16-bit symbol ids (int16 storage)");
+  return jaro_pairs_cpu_impl<uint16_t>(strs, lens, sc);
 }
 
 }  // namespace dblink

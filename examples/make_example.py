@@ -17,10 +17,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from dblink_amd.utils.synthdata import write_csv
 
-# --similarity -> (config key, similarity function) of the string attributes
+# --similarity -> (config key, similarity function, parameters) of the string
+# attributes
+EDIT_PARAMS = "threshold : 7.0, maxSimilarity : 10.0"
 SIMILARITY = {
-    "levenshtein": ("levSimFn", "LevenshteinSimilarityFn"),
-    "damerau": ("damSimFn", "DamerauLevenshteinSimilarityFn"),
+    "levenshtein": ("levSimFn", "LevenshteinSimilarityFn", EDIT_PARAMS),
+    "damerau": ("damSimFn", "DamerauLevenshteinSimilarityFn", EDIT_PARAMS),
+    "jaro": ("jaroSimFn", "JaroSimilarityFn", EDIT_PARAMS + ", prefixScale : 0.1"),
 }
 
 CONF = """dblink : {{
@@ -29,7 +32,7 @@ CONF = """dblink : {{
     constSimFn : {{ name : "ConstantSimilarityFn" }}
     {sim_key} : {{
         name : "{sim_name}",
-        parameters : {{ threshold : 7.0, maxSimilarity : 10.0 }}
+        parameters : {{ {sim_params} }}
     }}
 
     data : {{
@@ -90,7 +93,8 @@ def main():
                          "with per-file distortion probabilities)")
     ap.add_argument("--similarity", choices=sorted(SIMILARITY), default="levenshtein",
                     help="similarity function of the name attributes; damerau "
-                         "counts an adjacent swap as one edit")
+                         "counts an adjacent swap as one edit, jaro is Jaro "
+                         "similarity with the Winkler prefix boost")
     args = ap.parse_args()
 
     os.makedirs(args.out, exist_ok=True)
@@ -103,8 +107,8 @@ def main():
     # RLdata10000.conf Beta(10, 1000)): a weak prior at large n lets the
     # chain drift to a high-distortion mode
     alpha, beta = (10.0, 1000.0) if args.records >= 5000 else (0.5, 50.0)
-    sim_key, sim_name = SIMILARITY[args.similarity]
-    conf = CONF.format(sim_key=sim_key, sim_name=sim_name,
+    sim_key, sim_name, sim_params = SIMILARITY[args.similarity]
+    conf = CONF.format(sim_key=sim_key, sim_name=sim_name, sim_params=sim_params,
                        out=args.out, levels=args.levels, part_attrs=part_attrs,
                        samples=args.samples, burnin=args.burnin, thin=args.thin,
                        file_id_line=file_id_line, alpha=alpha, beta=beta,

@@ -3,7 +3,7 @@
 
     python scripts/sim_sweep_bench.py [--v 20000] [--repeats 5]
                                       [--parent-ext /path/to/parent/_C*.so]
-                                      [--metric {levenshtein,osa}]
+                                      [--metric {levenshtein,osa,jaro}]
 
 Three seeded domains of V values, each built as clusters of mutated copies so
 that the index is not empty:
@@ -21,7 +21,9 @@ driver stops at the first child that fails. The CPU pass uses the OpenMP
 thread count of the environment (OMP_NUM_THREADS). ``--metric osa`` times the
 transposition-aware sweeps instead (both the GPU and the CPU pass); a
 ``--parent-ext`` build older than that metric can only be compared under the
-default, ``levenshtein``. Prints one JSON document.
+default, ``levenshtein``. ``--metric jaro`` times ``jaro_pairs_gpu`` and
+``jaro_pairs_cpu`` (Jaro similarity with the Winkler prefix boost,
+``prefixScale`` 0.1) at the same threshold. Prints one JSON document.
 """
 
 import argparse
@@ -40,6 +42,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 THR, MSIM = 5.0, 10.0
+PREFIX_SCALE = 0.1  # --metric jaro
 
 
 def make_domain(case, V, seed=1234):
@@ -108,14 +111,19 @@ def worker(args):
            "metric": args.metric}
     # the default keeps the four-argument call an older extension understands
     extra = (True,) if args.metric == "osa" else ()
+    sweep = "sim_pairs"
+    if args.metric == "jaro":
+        sweep, extra = "jaro_pairs", (PREFIX_SCALE,)
     if args.kind == "gpu":
         assert torch.cuda.is_available(), "the GPU timing needs a GPU"
         tb, tl = tb.cuda(), tl.cuda()
-        run = lambda: C.sim_pairs_gpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
+        sweep_gpu = getattr(C, sweep + "_gpu")
+        run = lambda: sweep_gpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
         sync = torch.cuda.synchronize
     else:
         out["threads"] = torch.get_num_threads()
-        run = lambda: C.sim_pairs_cpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
+        sweep_cpu = getattr(C, sweep + "_cpu")
+        run = lambda: sweep_cpu(tb, tl, THR, MSIM, *extra)  # noqa: E731
         sync = lambda: None  # noqa: E731
     for _ in range(args.warmup):
         run()
@@ -165,8 +173,9 @@ def main():
     ap.add_argument("--timeout", type=int, default=390, help="seconds per child step")
     ap.add_argument("--ext", default=None, help="extension to time (default: this tree's)")
     ap.add_argument("--parent-ext", default=None, help="parent commit's built extension")
-    ap.add_argument("--metric", choices=["levenshtein", "osa"], default="levenshtein",
-                    help="edit distance of both sweeps (osa: adjacent swaps cost 1)")
+    ap.add_argument("--metric", choices=["levenshtein", "osa", "jaro"], default="levenshtein",
+                    help="metric of both sweeps (osa: adjacent swaps cost 1; jaro: "
+                         "Jaro similarity with the Winkler prefix boost)")
     ap.add_argument("--short-cpu", action="store_true",
                     help="also run the CPU pass on the short domain and compare nnz")
     ap.add_argument("--worker", action="store_true", help=argparse.SUPPRESS)
