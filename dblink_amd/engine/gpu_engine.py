@@ -368,14 +368,37 @@ class GpuEngine(CpuEngine):
         self._graphs_enabled = (
             os.environ.get("DBLINK_GRAPHS", "1") != "0" and world_size == 1
         )
+        # native sort / CSR / prefix glue between the sampling kernels
+        # (kernels.hip "Sweep glue"); DBLINK_FUSED_GLUE=0 keeps the torch
+        # expressions it replaces, as the A/B reference arm
+        self._fused = os.environ.get("DBLINK_FUSED_GLUE", "1") != "0"
+        self._resort_cap = int(self.C.resort_max_parts())
         self._loglik_buf = torch.zeros(256, dtype=torch.float64, device=device)
         A, F = self.model.A, self.model.F
-        self._packed = torch.zeros(2 + A * F + A + 1, dtype=torch.float64, device=device)
-        self._ctrl = torch.zeros(2, dtype=torch.int64, device=device)
-        self._ctrl_pin = torch.zeros(2, dtype=torch.int64, pin_memory=True)
-        self._theta_pin = torch.zeros((A, F), dtype=torch.float32, pin_memory=True)
+        # loglik, isolates, agg distortions, distortion histogram, error count
+        self._packed = torch.zeros(2 + A * F + A + 1 + 1, dtype=torch.float64,
+                                   device=device)
+        # per-sweep host inputs ({seed, iteration} and theta) share one pinned
+        # staging buffer and one device buffer: one host->device copy a sweep
+        self._stage_pin = torch.zeros(16 + 4 * A * F, dtype=torch.uint8,
+                                      pin_memory=True)
+        self._stage = torch.zeros(16 + 4 * A * F, dtype=torch.uint8, device=device)
+        self._ctrl_pin = self._stage_pin[:16].view(torch.int64)
+        self._theta_pin = self._stage_pin[16:].view(torch.float32).view(A, F)
+        self._ctrl = self._stage[:16].view(torch.int64)
+        self.model.theta = self._stage[16:].view(torch.float32).view(A, F)
         self._empty_i64 = torch.empty(0, dtype=torch.int64, device=device)
         self._counts = torch.zeros(1 + A * F + A + 1, dtype=torch.int64, device=device)
+        # fused-glue state: the one zero-filled counter block (loglik, summary
+        # counts, per-entity record counts, kobs), the CSR / re-sort buffers,
+        # and the partition offsets the re-sort leaves for the next sweep
+        self._zero_blk = None
+        self._zero_E = -1
+        self._ent_cnt = self._kobs = None
+        self._glue_key = None
+        self._ent_ptr = torch.zeros(self.num_partitions + 1, dtype=torch.int64,
+                                    device=device)
+        self._ent_ptr_valid = False
         # counting-sort inverted-index buffers (dense per-key histogram /
         # prefix / cursor over (partition, slot, value)); sized at first sweep
         self._idx_counts = None
@@ -451,6 +474,45 @@ class GpuEngine(CpuEngine):
             self._idx_counts.zero_()
         return nk
 
+    def _zero_counters(self, E):
+        """One fill for everything the fused sweep accumulates into: the
+        log-likelihood partials, the summary counts, the per-entity record
+        counts and kobs live in one block (typed views of it)."""
+        if self._zero_E == E:
+            self._zero_blk.zero_()
+            return
+        A = self.model.A
+        n_ll, n_c = 2 * self._loglik_buf.numel(), 2 * self._counts.numel()
+        # int32 words in front of the per-entity counters, which start on a
+        # 16-byte boundary (scan_excl's vector loads)
+        head = -(-(n_ll + n_c) // 4) * 4
+        blk = torch.zeros(head + E + E * A, dtype=torch.int32, device=self.device)
+        self._zero_blk = blk
+        self._loglik_buf = blk[:n_ll].view(torch.float64)
+        self._counts = blk[n_ll:n_ll + n_c].view(torch.int64)
+        self._ent_cnt = blk[head:head + E]
+        self._kobs = blk[head + E:]
+        self._zero_E = E
+
+    def _glue_bufs(self, E, R):
+        """Persistent outputs and scratch of the fused CSR and re-sort ops."""
+        if self._glue_key != (E, R):
+            dev, P = self.device, self.num_partitions
+            nh = int(self.C.resort_hist_size(E, P)) if P <= self._resort_cap else 0
+            self._glue = dict(
+                ent_rec_ptr=torch.zeros(E + 1, dtype=torch.int64, device=dev),
+                ent_rec_idx=torch.empty(R, dtype=torch.int64, device=dev),
+                hist=torch.empty(nh, dtype=torch.int32, device=dev),
+                tile_base=torch.empty(nh + 1, dtype=torch.int64, device=dev),
+                inv=torch.empty(E, dtype=torch.int32, device=dev),
+            )
+            self._glue_key = (E, R)
+        return self._glue
+
+    def _resort_fused_ok(self):
+        return (self._fused and self.world_size <= 1
+                and self.num_partitions <= self._resort_cap and self._tree_fits)
+
     def _heavy_active(self, R):
         return self._heavy_thresh > 0 and R >= self._heavy_min_records
 
@@ -493,6 +555,11 @@ class GpuEngine(CpuEngine):
 
     def _upload_tree(self):
         flat = self.partitioner.as_flat()
+        # the fused re-sort indexes LDS tables by leaf id
+        leaves = flat["a"][flat["kind"] == 0]
+        self._tree_fits = bool(
+            leaves.size and leaves.min() >= 0 and leaves.max() < self.num_partitions)
+        self._ent_ptr_valid = False  # a (re)loaded state: offsets not yet known
         self.flat_tree = {
             k: torch.from_numpy(np.ascontiguousarray(v.astype(np.int32))).to(self.device)
             for k, v in flat.items()
@@ -567,7 +634,8 @@ class GpuEngine(CpuEngine):
                 # summary stats are partition-agnostic: pack them from the
                 # pre-migration state and overlap the small all-reduce (on
                 # its own communicator) with the migration all-to-all
-                self._pack_summary(gs, loglik_done=True)
+                self._pack_summary(gs, loglik_done=True,
+                                   counts_zeroed=self._fused)
                 work = comm.all_reduce_sum_async(self._packed)
                 if self._overlap:
                     hist_add = None
@@ -633,8 +701,7 @@ class GpuEngine(CpuEngine):
         dev = self.device
 
         self._mark("start", graph_safe)
-        m.theta.copy_(self._theta_pin, non_blocking=True)
-        self._ctrl.copy_(self._ctrl_pin, non_blocking=True)
+        self._stage.copy_(self._stage_pin, non_blocking=True)  # ctrl + theta
         ctrl = self._ctrl
         seed, it = 0, 0  # kernels read the ctrl buffer
         # posting histogram possibly pre-built during the previous sweep's
@@ -643,10 +710,19 @@ class GpuEngine(CpuEngine):
         hist_pre = self._hist_ready
         self._hist_ready = False
 
-        ent_ptr = torch.searchsorted(
-            gs.ent_part.to(torch.int64).contiguous(),
-            torch.arange(self.num_partitions + 1, device=dev, dtype=torch.int64),
-        )
+        fused = self._fused
+        resort_fused = self._resort_fused_ok()
+        if fused:
+            self._zero_counters(E)
+            glue = self._glue_bufs(E, R)
+
+        if resort_fused and self._ent_ptr_valid:
+            ent_ptr = self._ent_ptr  # left by the previous sweep's re-sort
+        else:
+            ent_ptr = torch.searchsorted(
+                gs.ent_part.to(torch.int64).contiguous(),
+                torch.arange(self.num_partitions + 1, device=dev, dtype=torch.int64),
+            )
 
         # --- inverted index (counting sort over (partition, slot, value)) ----
         # Posting order within a key is arbitrary: the link kernels only
@@ -665,10 +741,18 @@ class GpuEngine(CpuEngine):
                     self.C.postings_hist(gs.ent_part, gs.ent_values, self._pair_a1,
                                          self._pair_a2, self._pair_v2, vmax,
                                          self._idx_counts)
-                torch.cumsum(self._idx_counts, 0, dtype=torch.int64,
-                             out=self._idx_ptr[1:])
-                if self._heavy_active(R) or \
-                        os.environ.get("DBLINK_FORCE_SORT", "") == "1":
+                heavy_sort = self._heavy_active(R) or \
+                    os.environ.get("DBLINK_FORCE_SORT", "") == "1"
+                if fused:
+                    # prefix and scatter cursor from one scan (one block while
+                    # the key space is small, the device scan above that)
+                    self.C.scan_excl(
+                        self._idx_counts, self._idx_ptr,
+                        self._idx_cursor[:0] if heavy_sort else self._idx_cursor)
+                else:
+                    torch.cumsum(self._idx_counts, 0, dtype=torch.int64,
+                                 out=self._idx_ptr[1:])
+                if heavy_sort:
                     # heavy sampler draws postings by segment INDEX, so the
                     # order within each key must be deterministic: sort
                     # (key * E + entity) — same boundaries as the prefix,
@@ -684,7 +768,8 @@ class GpuEngine(CpuEngine):
                     self.C.radix_sort_pairs_i64_i32(ekeys, keys_out, vals_in,
                                                     postings, end_bit, temp)
                 else:
-                    self._idx_cursor.copy_(self._idx_ptr[:-1])
+                    if not fused:
+                        self._idx_cursor.copy_(self._idx_ptr[:-1])
                     postings = torch.empty(T * E, dtype=torch.int32, device=dev)
                     self.C.postings_scatter(gs.ent_part, gs.ent_values,
                                             self._pair_a1, self._pair_a2,
@@ -751,22 +836,31 @@ class GpuEngine(CpuEngine):
                     self._num_pairs, seed, it, ctrl, rec_ent_new, gs.rec_ent,
                     self._err, self._heavy_stats,
                 )
-        gs.rec_ent.copy_(rec_ent_new)
-        self._mark("link", graph_safe)
+        if fused:
+            # --- entity -> records CSR, kobs and the link store: one op ------
+            self._mark("link", graph_safe)
+            ent_rec_ptr, ent_rec_idx = glue["ent_rec_ptr"], glue["ent_rec_idx"]
+            kobs = self._kobs
+            self.C.ent_csr_build(rec_ent_new, gs.rec_values, gs.rec_ent,
+                                 self._ent_cnt, kobs, ent_rec_ptr, ent_rec_idx)
+        else:
+            gs.rec_ent.copy_(rec_ent_new)
+            self._mark("link", graph_safe)
 
-        # --- entity -> records CSR -------------------------------------------
-        sorted_re, order = torch.sort(gs.rec_ent, stable=True)
-        ent_rec_ptr = torch.searchsorted(
-            sorted_re, torch.arange(E + 1, device=dev, dtype=torch.int64)
-        )
-        ent_rec_idx = order
+            # --- entity -> records CSR ---------------------------------------
+            sorted_re, order = torch.sort(gs.rec_ent, stable=True)
+            ent_rec_ptr = torch.searchsorted(
+                sorted_re, torch.arange(E + 1, device=dev, dtype=torch.int64)
+            )
+            ent_rec_idx = order
+
+            obs = gs.rec_values >= 0
+            kobs = torch.zeros(E * A, dtype=torch.int32, device=dev)
+            pair_idx = (gs.rec_ent.view(R, 1) * A
+                        + torch.arange(A, device=dev, dtype=torch.int64).view(1, A))
+            kobs.scatter_add_(0, pair_idx.reshape(-1), obs.reshape(-1).to(torch.int32))
 
         # --- phase 2: value update (in place) --------------------------------
-        obs = gs.rec_values >= 0
-        kobs = torch.zeros(E * A, dtype=torch.int32, device=dev)
-        pair_idx = (gs.rec_ent.view(R, 1) * A
-                    + torch.arange(A, device=dev, dtype=torch.int64).view(1, A))
-        kobs.scatter_add_(0, pair_idx.reshape(-1), obs.reshape(-1).to(torch.int32))
         # kernels self-select on kobs: no host-side pair lists, no sync
         pair_wave = self._empty_i64
         if getattr(self, "value_allwave", False):
@@ -786,7 +880,8 @@ class GpuEngine(CpuEngine):
 
         self._mark("value", graph_safe)
         # --- phase 3: distortion update (log-likelihood fused in) ------------
-        self._loglik_buf.zero_()
+        if not fused:
+            self._loglik_buf.zero_()
         self.C.distortion_update(
             gs.rec_values, gs.rec_dist, gs.rec_file, gs.rec_gid, gs.rec_ent,
             gs.ent_values, m.theta, m.phi, m.norm_lin, m.self_expsim, m.voff,
@@ -796,27 +891,44 @@ class GpuEngine(CpuEngine):
 
         self._mark("distortion", graph_safe)
         # --- partition reassignment ------------------------------------------
-        ent_part_new = torch.empty_like(gs.ent_part)
-        self.C.kd_descent(
-            gs.ent_values, self.flat_tree["kind"], self.flat_tree["attr"],
-            self.flat_tree["a"], self.flat_tree["b"], self.flat_tree["rset"],
-            ent_part_new,
-        )
-        gs.ent_part.copy_(ent_part_new)
-        self._mark("kd", graph_safe)
+        if not resort_fused:
+            ent_part_new = torch.empty_like(gs.ent_part)
+            self.C.kd_descent(
+                gs.ent_values, self.flat_tree["kind"], self.flat_tree["attr"],
+                self.flat_tree["a"], self.flat_tree["b"], self.flat_tree["rset"],
+                ent_part_new,
+            )
+            gs.ent_part.copy_(ent_part_new)
+            self._mark("kd", graph_safe)
 
-        self._finish_local(gs, gs_out, ent_rec_ptr, graph_safe)
+        self._finish_local(gs, gs_out, ent_rec_ptr, graph_safe, resort_fused)
 
-    def _finish_local(self, gs, gs_out, ent_rec_ptr, graph_safe):
+    def _finish_local(self, gs, gs_out, ent_rec_ptr, graph_safe, resort_fused):
         """Single-rank sweep tail: re-sort by partition id and pack the
         summary. isolate COUNT is permutation-invariant, so the pre-sort CSR
         is still valid for the summary counts."""
         if self.world_size > 1:
             return
-        self._sort_into(gs, gs_out)
+        if resort_fused:
+            self._resort_into(gs, gs_out)
+        else:
+            self._sort_into(gs, gs_out)
         self._mark("sort", graph_safe)
-        self._pack_summary(gs_out, ent_rec_ptr=ent_rec_ptr, loglik_done=True)
+        self._pack_summary(gs_out, ent_rec_ptr=ent_rec_ptr, loglik_done=True,
+                           counts_zeroed=self._fused)
         self._mark("summary", graph_safe)
+
+    def _resort_into(self, gs: GpuStateTensors, out: GpuStateTensors):
+        """KD descent and _sort_into as one native op (same results), which
+        also leaves the next sweep's partition offsets in ``_ent_ptr``."""
+        t, glue = self.flat_tree, self._glue_bufs(gs.E, gs.R)
+        self.C.partition_resort(
+            gs.ent_values, gs.ent_part, gs.rec_ent, t["kind"], t["attr"], t["a"],
+            t["b"], t["rset"], self.num_partitions, glue["hist"],
+            glue["tile_base"], glue["inv"], out.ent_part, out.ent_values,
+            out.rec_ent, out.rec_part, self._ent_ptr,
+        )
+        self._ent_ptr_valid = True
 
     def _sort_into(self, gs: GpuStateTensors, out: GpuStateTensors):
         """Re-sort ENTITIES by partition id, gathering straight into the
@@ -837,10 +949,12 @@ class GpuEngine(CpuEngine):
 
     # ---- summary -------------------------------------------------------------
 
-    def _pack_summary(self, gs: GpuStateTensors, ent_rec_ptr=None, loglik_done=False):
+    def _pack_summary(self, gs: GpuStateTensors, ent_rec_ptr=None, loglik_done=False,
+                      counts_zeroed=False):
         m = self.model
         E = gs.E
-        self._counts.zero_()
+        if not counts_zeroed:  # the fused sweep zeroed them with its one fill
+            self._counts.zero_()
         if not loglik_done:  # standalone summary (no sweep ran this iteration)
             self._loglik_buf.zero_()
             self.C.summary_loglik(
@@ -855,7 +969,7 @@ class GpuEngine(CpuEngine):
             )
         self.C.summary_counts(
             gs.rec_dist, gs.rec_file, ent_rec_ptr, E, self._counts,
-            self._loglik_buf, self._packed,
+            self._loglik_buf, self._packed, self._err,
         )
 
     def _read_summary(self, state: ChainState) -> SummaryVars:
@@ -875,7 +989,9 @@ class GpuEngine(CpuEngine):
             host, self._summary_host = self._summary_host, None
         else:
             host = packed.cpu().numpy()
-        err = int(self._err.cpu())
+        # the error count rides in the packed buffer's last slot (summed over
+        # ranks it is still nonzero iff any rank erred): one blocking read
+        err = int(round(host[-1]))
         if err:
             raise RuntimeError(
                 f"{err} empty candidate sets in link update (invariant violated)"
@@ -884,7 +1000,7 @@ class GpuEngine(CpuEngine):
             num_isolates=int(round(host[1])),
             log_likelihood=float(host[0]),
             agg_distortions=host[2 : 2 + A * F].reshape(A, F).astype(np.int64),
-            rec_distortions=host[2 + A * F :].astype(np.int64),
+            rec_distortions=host[2 + A * F : -1].astype(np.int64),
         )
         add_prior_terms(out, self.cache, state.dist_probs)
         return out

@@ -171,7 +171,22 @@ void scalar_score_bench(torch::Tensor rcode, torch::Tensor rbonus,
                         torch::Tensor ecode, torch::Tensor score);
 void summary_counts(torch::Tensor rec_dist, torch::Tensor rec_file,
                     torch::Tensor ent_rec_ptr, int64_t E, torch::Tensor counts,
-                    torch::Tensor loglik, torch::Tensor packed);
+                    torch::Tensor loglik, torch::Tensor packed, torch::Tensor err);
+void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor);
+void ent_csr_build(torch::Tensor rec_ent_new, torch::Tensor rec_values,
+                   torch::Tensor rec_ent, torch::Tensor ent_cnt,
+                   torch::Tensor kobs, torch::Tensor ent_rec_ptr,
+                   torch::Tensor ent_rec_idx);
+int64_t resort_max_parts();
+int64_t resort_hist_size(int64_t E, int64_t P);
+void partition_resort(torch::Tensor ent_values, torch::Tensor ent_part,
+                      torch::Tensor rec_ent, torch::Tensor node_kind,
+                      torch::Tensor node_attr, torch::Tensor node_a,
+                      torch::Tensor node_b, torch::Tensor rset, int64_t P,
+                      torch::Tensor hist, torch::Tensor tile_base,
+                      torch::Tensor inv, torch::Tensor out_ent_part,
+                      torch::Tensor out_ent_values, torch::Tensor out_rec_ent,
+                      torch::Tensor out_rec_part, torch::Tensor ent_ptr);
 void kd_descent(torch::Tensor ent_values, torch::Tensor node_kind,
                 torch::Tensor node_attr, torch::Tensor node_a, torch::Tensor node_b,
                 torch::Tensor rset, torch::Tensor ent_part_out);
@@ -244,7 +259,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "hipGraph-safe rocprim radix sort (persistent workspace)");
   m.def("link_update_heavy", &dblink::link_update_heavy,
         "hierarchical (A*) Gumbel-max link update for huge candidate sets");
-  m.def("summary_counts", &dblink::summary_counts, "fused summary counts + pack");
+  m.def("summary_counts", &dblink::summary_counts,
+        "fused summary counts + pack (+ the error count in the last slot)");
+  m.def("scan_excl", &dblink::scan_excl,
+        "exclusive int32 -> int64 prefix with an optional int32 cursor copy");
+  m.def("ent_csr_build", &dblink::ent_csr_build,
+        "entity -> records CSR (stable order) + kobs + link store");
+  m.def("resort_max_parts", &dblink::resort_max_parts,
+        "partition-count cap of partition_resort");
+  m.def("resort_hist_size", &dblink::resort_hist_size,
+        "histogram counters partition_resort needs");
+  m.def("partition_resort", &dblink::partition_resort,
+        "K9 KD descent + stable partition re-sort + record remap");
   m.def("set_value_stats", &dblink::set_value_stats,
         "install the optional value-phase work-counter buffer");
   m.def("set_value_ktables", &dblink::set_value_ktables,

@@ -12,6 +12,10 @@
 //              build_ekeys_stable (+ rocprim radix sort), classify_modes
 //   --     mfma_score / scalar_score — matrix-core scoring experiment
 //   K9     kd_descent_kernel — flat KD-tree partition reassignment
+//   --     scan_excl, csr_count / _scatter / _order, resort_hist / _scatter /
+//              _remap — the integer glue of the sweep (index prefix, entity ->
+//              records CSR + kobs, KD descent fused with the stable partition
+//              re-sort)
 //   K1     sim_pairs_kernel — bit-parallel Levenshtein / OSA domain sweep
 //          jaro_pairs_kernel — bit-parallel Jaro(-Winkler) domain sweep
 //
@@ -2107,15 +2111,18 @@ __global__ void summary_counts_kernel(
   }
 }
 
-// Pack loglik + counts into the f64 summary buffer (one tiny launch).
+// Pack loglik + counts (+ the sweep's error count, so the host reads one
+// buffer) into the f64 summary buffer (one tiny launch).
 __global__ void summary_finalize_kernel(
     const double* __restrict__ loglik, const unsigned long long* __restrict__ counts,
-    int n_counts, double* __restrict__ packed) {
+    int n_counts, const int* __restrict__ err,  // [1] or null
+    double* __restrict__ packed) {              // [1 + n_counts (+ 1 with err)]
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) {
     double s = 0.0;
     for (int j = 0; j < 256; ++j) s += loglik[j];
     packed[0] = s;
+    if (err) packed[1 + n_counts] = (double)err[0];
   }
   if (i < n_counts) packed[1 + i] = (double)counts[i];
 }
@@ -2242,13 +2249,12 @@ void scalar_score_bench(torch::Tensor rcode, torch::Tensor rbonus,
 // K9a: KD-tree descent (flat tree, partitioning.py as_flat layout)
 // ---------------------------------------------------------------------------
 
-__global__ void kd_descent_kernel(
+// Leaf partition id of entity e.
+DBL_D int32_t kd_leaf(
     const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
     const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
     const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
-    int64_t E, int A, int32_t* __restrict__ ent_part_out) {
-  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (e >= E) return;
+    int64_t e, int A) {
   int nid = 0;
   while (node_kind[nid] != 0) {
     const int a = node_attr[nid];
@@ -2262,7 +2268,292 @@ __global__ void kd_descent_kernel(
     }
     nid = 2 * nid + (right ? 2 : 1);
   }
-  ent_part_out[e] = node_a[nid];
+  return node_a[nid];
+}
+
+__global__ void kd_descent_kernel(
+    const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
+    const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
+    const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
+    int64_t E, int A, int32_t* __restrict__ ent_part_out) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= E) return;
+  ent_part_out[e] =
+      kd_leaf(ent_values, node_kind, node_attr, node_a, node_b, rset, e, A);
+}
+
+// ---------------------------------------------------------------------------
+// Sweep glue: the integer bookkeeping between the sampling kernels, as plain
+// launches over persistent buffers (no allocation, no stream workspace, so
+// all of it is hipGraph-safe). Every output equals, element for element, the
+// torch expression it stands in for (gpu_engine.py keeps those as the
+// DBLINK_FUSED_GLUE=0 arm):
+//   scan_excl_kernel     exclusive prefix of int32 counts -> int64 ptr[n+1]
+//                        (+ an int32 cursor copy), one block
+//   csr_count / _scatter / _order
+//                        entity -> records CSR in stable order (= stable sort
+//                        of rec_ent) with the kobs counts taken in the count
+//                        pass
+//   resort_hist / _scatter / _remap
+//                        KD descent + stable counting sort of the entities by
+//                        partition id (= stable argsort of ent_part), and the
+//                        record remap through the inverse permutation
+// ---------------------------------------------------------------------------
+constexpr int GL_THREADS = 1024;  // block (= entity tile) of the scan and re-sort
+constexpr int GL_WAVES = GL_THREADS / WAVE;
+// partitions the re-sort ranks in LDS (GL_WAVES * 256 * 4 B = 16 KiB); above
+// it the engine keeps the torch argsort path
+constexpr int RESORT_MAX_PARTS = 256;
+// single-block scans stay cheaper than the two-kernel device scan up to about
+// this many counters (32 tiles of 4096); above it launchers call cumsum
+constexpr int64_t SCAN_SINGLE_MAX = 1 << 17;
+constexpr int CSR_SERIAL_SEG = 32;  // longest segment one thread orders alone
+
+// One thread's four consecutive counters of a tile. All of the scan's traffic
+// goes through ONE compute unit, so it has to be coalesced: with 16-byte
+// aligned buffers (vec) a thread moves its four counters as one 16-byte load
+// and its results as 16-byte stores; otherwise element by element.
+DBL_D void scan_load4(const int32_t* __restrict__ counts, int64_t i0, int64_t n,
+                      bool vec, int32_t (&c)[4]) {
+  if (vec && i0 + 4 <= n) {
+    const int4 v = *reinterpret_cast<const int4*>(counts + i0);
+    c[0] = v.x; c[1] = v.y; c[2] = v.z; c[3] = v.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] = (i0 + j < n) ? counts[i0 + j] : 0;
+  }
+}
+
+__global__ __launch_bounds__(GL_THREADS) void scan_excl_kernel(
+    const int32_t* __restrict__ counts, int64_t n,
+    int64_t* __restrict__ ptr,       // [n + 1]
+    int32_t* __restrict__ cursor,    // [n] copy of ptr[:n], or null
+    bool vec) {                      // all three buffers 16-byte aligned
+  __shared__ int64_t wave_tot[GL_WAVES];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  constexpr int64_t TILE = GL_THREADS * 4;
+  int64_t carry = 0;
+  int32_t c[4], c_next[4];
+  scan_load4(counts, (int64_t)threadIdx.x * 4, n, vec, c_next);
+  for (int64_t base = 0; base < n; base += TILE) {
+    const int64_t i0 = base + (int64_t)threadIdx.x * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) c[j] = c_next[j];
+    // the next tile's loads fly while this one is scanned
+    if (base + TILE < n) scan_load4(counts, i0 + TILE, n, vec, c_next);
+    const int64_t mine = (int64_t)c[0] + c[1] + c[2] + c[3];
+    int64_t inc = mine;  // inclusive scan across the wave
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      const int64_t o = __shfl_up(inc, off);
+      if (lane >= off) inc += o;
+    }
+    if (lane == WAVE - 1) wave_tot[wave] = inc;
+    __syncthreads();
+    int64_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < GL_WAVES; ++w) {
+      const int64_t t = wave_tot[w];
+      if (w < wave) before += t;
+      total += t;
+    }
+    const int64_t x0 = carry + before + inc - mine;
+    const int64_t x1 = x0 + c[0], x2 = x1 + c[1], x3 = x2 + c[2];
+    if (vec && i0 + 4 <= n) {
+      longlong2* p2 = reinterpret_cast<longlong2*>(ptr + i0);
+      p2[0] = make_longlong2(x0, x1);
+      p2[1] = make_longlong2(x2, x3);
+      if (cursor)
+        *reinterpret_cast<int4*>(cursor + i0) =
+            make_int4((int32_t)x0, (int32_t)x1, (int32_t)x2, (int32_t)x3);
+    } else {
+      const int64_t x[4] = {x0, x1, x2, x3};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        if (i0 + j < n) {
+          ptr[i0 + j] = x[j];
+          if (cursor) cursor[i0 + j] = (int32_t)x[j];
+        }
+      }
+    }
+    carry += total;
+    __syncthreads();  // wave_tot is rewritten by the next tile
+  }
+  if (threadIdx.x == 0) ptr[n] = carry;
+}
+
+// Count pass: records per entity, observed values per (entity, attribute),
+// and the store of the new links into the state's rec_ent.
+__global__ void csr_count_kernel(
+    const int64_t* __restrict__ rec_ent_new, const int32_t* __restrict__ rec_values,
+    int64_t R, int A,
+    int64_t* __restrict__ rec_ent,    // [R] state copy of the links, or null
+    int32_t* __restrict__ ent_cnt,    // [E] zeroed
+    int32_t* __restrict__ kobs) {     // [E * A] zeroed
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int64_t e = rec_ent_new[r];
+  if (rec_ent) rec_ent[r] = e;
+  atomicAdd(&ent_cnt[e], 1);
+  for (int a = 0; a < A; ++a)
+    if (rec_values[r * A + a] >= 0) atomicAdd(&kobs[e * A + a], 1);
+}
+
+// Scatter pass: each record takes a slot of its entity's segment by counting
+// ent_cnt back down (order within a segment is arbitrary until csr_order).
+// Leaves ent_cnt all zero.
+__global__ void csr_scatter_kernel(
+    const int64_t* __restrict__ rec_ent, const int64_t* __restrict__ ent_rec_ptr,
+    int64_t R, int32_t* __restrict__ ent_cnt, int64_t* __restrict__ ent_rec_idx) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int64_t e = rec_ent[r];
+  const int32_t k = atomicSub(&ent_cnt[e], 1);
+  ent_rec_idx[ent_rec_ptr[e] + k - 1] = r;
+}
+
+// Order pass: ascending record index within every segment. One thread sorts
+// a short segment in place; a segment longer than CSR_SERIAL_SEG is rebuilt
+// by its block as an ordered compaction over all records (O(R) per such
+// entity: correct at any length, meant for the rare oversized cluster).
+constexpr int CSR_ORDER_THREADS = 256;
+
+__global__ __launch_bounds__(CSR_ORDER_THREADS) void csr_order_kernel(
+    const int64_t* __restrict__ rec_ent, const int64_t* __restrict__ ent_rec_ptr,
+    int64_t E, int64_t R, int64_t* ent_rec_idx) {
+  __shared__ int32_t n_long;
+  __shared__ int64_t long_ent[CSR_ORDER_THREADS];
+  __shared__ int32_t wave_cnt[CSR_ORDER_THREADS / WAVE];
+  if (threadIdx.x == 0) n_long = 0;
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e < E) {
+    const int64_t lo = ent_rec_ptr[e];
+    const int64_t len = ent_rec_ptr[e + 1] - lo;
+    if (len > CSR_SERIAL_SEG) {
+      long_ent[atomicAdd(&n_long, 1)] = e;
+    } else {
+      for (int64_t i = 1; i < len; ++i) {  // insertion sort
+        const int64_t v = ent_rec_idx[lo + i];
+        int64_t j = i;
+        while (j > 0 && ent_rec_idx[lo + j - 1] > v) {
+          ent_rec_idx[lo + j] = ent_rec_idx[lo + j - 1];
+          --j;
+        }
+        ent_rec_idx[lo + j] = v;
+      }
+    }
+  }
+  __syncthreads();
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int nl = n_long;
+  for (int k = 0; k < nl; ++k) {
+    const int64_t le = long_ent[k];
+    int64_t out = ent_rec_ptr[le];
+    for (int64_t base = 0; base < R; base += CSR_ORDER_THREADS) {
+      const int64_t r = base + threadIdx.x;
+      const bool hit = r < R && rec_ent[r] == le;
+      const unsigned long long m = __ballot(hit);
+      if (lane == 0) wave_cnt[wave] = __popcll(m);
+      __syncthreads();
+      int before = 0, total = 0;
+#pragma unroll
+      for (int w = 0; w < CSR_ORDER_THREADS / WAVE; ++w) {
+        const int t = wave_cnt[w];
+        if (w < wave) before += t;
+        total += t;
+      }
+      if (hit)
+        ent_rec_idx[out + before + __popcll(m & ((1ull << lane) - 1ull))] = r;
+      out += total;
+      __syncthreads();  // wave_cnt is rewritten by the next tile
+    }
+  }
+}
+
+// Re-sort pass 1: KD descent of one tile of GL_THREADS entities and the
+// tile's partition histogram, stored partition-major so one flat exclusive
+// scan gives every (partition, tile) its first output slot.
+__global__ __launch_bounds__(GL_THREADS) void resort_hist_kernel(
+    const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
+    const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
+    const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
+    int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ ent_part_new,  // [E] unsorted new partition ids
+    int32_t* __restrict__ hist) {        // [P * n_tiles]
+  __shared__ int32_t h[RESORT_MAX_PARTS];
+  for (int i = threadIdx.x; i < P; i += GL_THREADS) h[i] = 0;
+  __syncthreads();
+  const int64_t e = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x;
+  if (e < E) {
+    const int32_t p =
+        kd_leaf(ent_values, node_kind, node_attr, node_a, node_b, rset, e, A);
+    ent_part_new[e] = p;
+    // the launcher's caller checks every leaf id against P; the guard keeps
+    // a bad tree from writing outside the table
+    if ((uint32_t)p < (uint32_t)P) atomicAdd(&h[p], 1);
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < P; i += GL_THREADS)
+    hist[(int64_t)i * n_tiles + blockIdx.x] = h[i];
+}
+
+// Re-sort pass 2 (after the scan of hist): stable scatter. An entity's slot
+// is its (partition, tile) base + same-partition entities of earlier waves in
+// the tile + earlier lanes of its wave, i.e. entity order within a partition
+// is kept. Also emits the next sweep's partition offsets.
+__global__ __launch_bounds__(GL_THREADS) void resort_scatter_kernel(
+    const int32_t* __restrict__ ent_part_new, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ tile_base,  // [P * n_tiles + 1] scanned hist
+    int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ out_part,     // [E]
+    int32_t* __restrict__ out_values,   // [E, A]
+    int32_t* __restrict__ inv,          // [E] old index -> new index
+    int64_t* __restrict__ ent_ptr) {    // [P + 1]
+  __shared__ int32_t wave_cnt[GL_WAVES * RESORT_MAX_PARTS];
+  for (int i = threadIdx.x; i < GL_WAVES * P; i += GL_THREADS) wave_cnt[i] = 0;
+  __syncthreads();
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wave = threadIdx.x / WAVE;
+  const int64_t e = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x;
+  int32_t p = e < E ? ent_part_new[e] : -1;
+  if ((uint32_t)p >= (uint32_t)P) p = -1;  // see resort_hist_kernel
+  int rank = 0;
+  unsigned long long pending = __ballot(p >= 0);
+  while (pending) {  // one round per distinct partition in the wave
+    const int leader = __ffsll((long long)pending) - 1;
+    const int32_t lp = __shfl(p, leader);
+    const unsigned long long m = __ballot(p == lp);
+    if (p == lp) rank = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == leader) wave_cnt[wave * P + lp] = __popcll(m);
+    pending &= ~m;
+  }
+  __syncthreads();
+  if (p >= 0) {
+    int before = 0;
+    for (int w = 0; w < wave; ++w) before += wave_cnt[w * P + p];
+    const int64_t dst = tile_base[(int64_t)p * n_tiles + blockIdx.x] + before + rank;
+    out_part[dst] = p;
+    for (int a = 0; a < A; ++a) out_values[dst * A + a] = ent_values[e * A + a];
+    inv[e] = (int32_t)dst;
+  }
+  if (blockIdx.x == 0 && threadIdx.x <= P)
+    ent_ptr[threadIdx.x] =
+        threadIdx.x < P ? tile_base[(int64_t)threadIdx.x * n_tiles] : E;
+}
+
+// Re-sort pass 3: records stay put; their links follow the permutation.
+__global__ void resort_remap_kernel(
+    const int64_t* __restrict__ rec_ent, const int32_t* __restrict__ inv,
+    const int32_t* __restrict__ ent_part_new, int64_t R,
+    int64_t* __restrict__ out_rec_ent, int32_t* __restrict__ out_rec_part) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= R) return;
+  const int64_t e = rec_ent[r];
+  out_rec_ent[r] = inv[e];
+  out_rec_part[r] = ent_part_new[e];
 }
 
 // ---------------------------------------------------------------------------
@@ -3246,12 +3537,17 @@ void build_keys(torch::Tensor ent_part, torch::Tensor ent_values,
 
 void summary_counts(torch::Tensor rec_dist, torch::Tensor rec_file,
                     torch::Tensor ent_rec_ptr, int64_t E, torch::Tensor counts,
-                    torch::Tensor loglik, torch::Tensor packed) {
+                    torch::Tensor loglik, torch::Tensor packed,
+                    torch::Tensor err) {
   const int64_t R = rec_dist.size(0);
   const int A = (int)rec_dist.size(1);
   const int F = (int)((counts.numel() - 1 - (A + 1)) / A);
   const int64_t total = E + R;
   const int n_counts = (int)counts.numel();
+  // err (int32 [1], may be empty) lands in one extra slot past the counts
+  const bool with_err = err.numel() > 0;
+  TORCH_CHECK(packed.numel() >= 1 + n_counts + (with_err ? 1 : 0),
+              "packed summary buffer too small");
   if (total > 0) {
     dim3 grid((unsigned)((total + 255) / 256));
     hipLaunchKernelGGL(summary_counts_kernel, grid, dim3(256),
@@ -3266,7 +3562,148 @@ void summary_counts(torch::Tensor rec_dist, torch::Tensor rec_file,
                      at::cuda::getCurrentCUDAStream(),
                      loglik.data_ptr<double>(),
                      (const unsigned long long*)counts.data_ptr<int64_t>(),
-                     n_counts, packed.data_ptr<double>());
+                     n_counts, with_err ? err.data_ptr<int>() : nullptr,
+                     packed.data_ptr<double>());
+}
+
+// Exclusive prefix of int32 counts [n] into ptr [n + 1] (int64), with an
+// optional int32 cursor [n] = ptr[:n]: one block up to SCAN_SINGLE_MAX
+// counters, cumsum (+ copy) above.
+void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor) {
+  CHECK_GPU(counts);
+  CHECK_CONTIG(counts);
+  CHECK_CONTIG(ptr);
+  CHECK_CONTIG(cursor);
+  const int64_t n = counts.numel();
+  TORCH_CHECK(counts.scalar_type() == torch::kInt32 &&
+              ptr.scalar_type() == torch::kInt64, "scan_excl: int32 -> int64");
+  TORCH_CHECK(ptr.numel() == n + 1, "scan_excl: ptr must hold n + 1 entries");
+  const bool with_cursor = cursor.numel() > 0;
+  TORCH_CHECK(!with_cursor || (cursor.numel() == n &&
+                               cursor.scalar_type() == torch::kInt32),
+              "scan_excl: cursor must be int32 [n]");
+  if (n <= SCAN_SINGLE_MAX) {
+    const auto misaligned = [](const void* p) {
+      return (reinterpret_cast<uintptr_t>(p) & 15) != 0;
+    };
+    const bool vec = !misaligned(counts.data_ptr()) && !misaligned(ptr.data_ptr()) &&
+                     !(with_cursor && misaligned(cursor.data_ptr()));
+    hipLaunchKernelGGL(scan_excl_kernel, dim3(1), dim3(GL_THREADS), 0,
+                       at::cuda::getCurrentCUDAStream(),
+                       counts.data_ptr<int32_t>(), n, ptr.data_ptr<int64_t>(),
+                       with_cursor ? cursor.data_ptr<int32_t>() : nullptr, vec);
+    return;
+  }
+  ptr.narrow(0, 0, 1).zero_();
+  auto tail = ptr.narrow(0, 1, n);
+  at::cumsum_out(tail, counts, 0, torch::kInt64);
+  if (with_cursor) cursor.copy_(ptr.narrow(0, 0, n));
+}
+
+// Entity -> records CSR in stable order, the kobs counts and the store of
+// the new links, from zeroed counters (left zeroed: ent_cnt; filled: kobs).
+void ent_csr_build(torch::Tensor rec_ent_new, torch::Tensor rec_values,
+                   torch::Tensor rec_ent, torch::Tensor ent_cnt,
+                   torch::Tensor kobs, torch::Tensor ent_rec_ptr,
+                   torch::Tensor ent_rec_idx) {
+  CHECK_GPU(rec_ent_new);
+  CHECK_CONTIG(rec_ent_new);
+  CHECK_CONTIG(rec_values);
+  CHECK_CONTIG(rec_ent);
+  CHECK_CONTIG(ent_cnt);
+  CHECK_CONTIG(kobs);
+  CHECK_CONTIG(ent_rec_idx);
+  const int64_t R = rec_values.size(0);
+  const int A = (int)rec_values.size(1);
+  const int64_t E = ent_cnt.numel();
+  TORCH_CHECK(rec_ent_new.numel() == R && ent_rec_idx.numel() == R &&
+              ent_rec_ptr.numel() == E + 1 && kobs.numel() == E * A,
+              "ent_csr_build: shape mismatch");
+  TORCH_CHECK(rec_ent.numel() == 0 || rec_ent.numel() == R,
+              "ent_csr_build: rec_ent must be empty or [R]");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const dim3 rgrid((unsigned)((R + 255) / 256));
+  if (R > 0)
+    hipLaunchKernelGGL(csr_count_kernel, rgrid, dim3(256), 0, stream,
+                       rec_ent_new.data_ptr<int64_t>(),
+                       rec_values.data_ptr<int32_t>(), R, A,
+                       rec_ent.numel() ? rec_ent.data_ptr<int64_t>() : nullptr,
+                       ent_cnt.data_ptr<int32_t>(), kobs.data_ptr<int32_t>());
+  scan_excl(ent_cnt, ent_rec_ptr, ent_cnt.narrow(0, 0, 0));  // no cursor
+  if (R == 0) return;
+  hipLaunchKernelGGL(csr_scatter_kernel, rgrid, dim3(256), 0, stream,
+                     rec_ent_new.data_ptr<int64_t>(),
+                     ent_rec_ptr.data_ptr<int64_t>(), R,
+                     ent_cnt.data_ptr<int32_t>(),
+                     ent_rec_idx.data_ptr<int64_t>());
+  hipLaunchKernelGGL(csr_order_kernel,
+                     dim3((unsigned)((E + CSR_ORDER_THREADS - 1) / CSR_ORDER_THREADS)),
+                     dim3(CSR_ORDER_THREADS), 0, stream,
+                     rec_ent_new.data_ptr<int64_t>(),
+                     ent_rec_ptr.data_ptr<int64_t>(), E, R,
+                     ent_rec_idx.data_ptr<int64_t>());
+}
+
+int64_t resort_max_parts() { return RESORT_MAX_PARTS; }
+
+static int64_t resort_tiles(int64_t E) { return (E + GL_THREADS - 1) / GL_THREADS; }
+
+// Histogram counters partition_resort needs for E entities in P partitions
+// (its scanned bases take one more).
+int64_t resort_hist_size(int64_t E, int64_t P) { return P * resort_tiles(E); }
+
+// KD descent + stable re-sort of the entities by partition id into the other
+// buffer set, the record remap, and the next sweep's partition offsets.
+// ent_part receives the unsorted new partition ids (as kd_descent + copy did).
+void partition_resort(
+    torch::Tensor ent_values, torch::Tensor ent_part, torch::Tensor rec_ent,
+    torch::Tensor node_kind, torch::Tensor node_attr, torch::Tensor node_a,
+    torch::Tensor node_b, torch::Tensor rset, int64_t P,
+    torch::Tensor hist, torch::Tensor tile_base, torch::Tensor inv,
+    torch::Tensor out_ent_part, torch::Tensor out_ent_values,
+    torch::Tensor out_rec_ent, torch::Tensor out_rec_part,
+    torch::Tensor ent_ptr) {
+  CHECK_GPU(ent_values);
+  CHECK_CONTIG(ent_values);
+  CHECK_CONTIG(ent_part);
+  CHECK_CONTIG(rec_ent);
+  CHECK_CONTIG(out_ent_part);
+  CHECK_CONTIG(out_ent_values);
+  CHECK_CONTIG(out_rec_ent);
+  CHECK_CONTIG(out_rec_part);
+  const int64_t E = ent_values.size(0);
+  const int A = (int)ent_values.size(1);
+  const int64_t R = rec_ent.numel();
+  TORCH_CHECK(P >= 1 && P <= RESORT_MAX_PARTS, "partition_resort supports 1..",
+              RESORT_MAX_PARTS, " partitions");
+  TORCH_CHECK(E >= 1 && E <= INT32_MAX, "partition_resort: entity count out of range");
+  const int64_t n_tiles = resort_tiles(E);
+  TORCH_CHECK(hist.numel() == P * n_tiles && tile_base.numel() == P * n_tiles + 1 &&
+              inv.numel() == E && ent_ptr.numel() == P + 1 &&
+              ent_part.numel() == E && out_ent_part.numel() == E &&
+              out_ent_values.numel() == E * A && out_rec_ent.numel() == R &&
+              out_rec_part.numel() == R,
+              "partition_resort: shape mismatch");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  hipLaunchKernelGGL(resort_hist_kernel, dim3((unsigned)n_tiles), dim3(GL_THREADS),
+                     0, stream, ent_values.data_ptr<int32_t>(),
+                     node_kind.data_ptr<int32_t>(), node_attr.data_ptr<int32_t>(),
+                     node_a.data_ptr<int32_t>(), node_b.data_ptr<int32_t>(),
+                     rset.data_ptr<int32_t>(), E, A, (int)P, n_tiles,
+                     ent_part.data_ptr<int32_t>(), hist.data_ptr<int32_t>());
+  scan_excl(hist, tile_base, hist.narrow(0, 0, 0));  // no cursor
+  hipLaunchKernelGGL(resort_scatter_kernel, dim3((unsigned)n_tiles),
+                     dim3(GL_THREADS), 0, stream, ent_part.data_ptr<int32_t>(),
+                     ent_values.data_ptr<int32_t>(), tile_base.data_ptr<int64_t>(),
+                     E, A, (int)P, n_tiles, out_ent_part.data_ptr<int32_t>(),
+                     out_ent_values.data_ptr<int32_t>(), inv.data_ptr<int32_t>(),
+                     ent_ptr.data_ptr<int64_t>());
+  if (R > 0)
+    hipLaunchKernelGGL(resort_remap_kernel, dim3((unsigned)((R + 255) / 256)),
+                       dim3(256), 0, stream, rec_ent.data_ptr<int64_t>(),
+                       inv.data_ptr<int32_t>(), ent_part.data_ptr<int32_t>(), R,
+                       out_rec_ent.data_ptr<int64_t>(),
+                       out_rec_part.data_ptr<int32_t>());
 }
 
 void kd_descent(
