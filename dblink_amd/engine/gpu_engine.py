@@ -449,6 +449,31 @@ class GpuEngine(CpuEngine):
         # routing engages above this record count and turns graphs off.
         self._heavy_min_records = int(os.environ.get("DBLINK_HEAVY_MIN", "50000"))
         self._heavy_stats = torch.zeros(4, dtype=torch.int64, device=device)
+        # wave-scan records whose base list exceeds _split_len go on a device
+        # list and get a block each (link_update_split_kernel) from a static
+        # grid; DBLINK_LINK_SPLIT=0 keeps them on the wave kernel (A/B;
+        # draws are bitwise identical)
+        self._split_len = (
+            int(os.environ.get("DBLINK_LINK_SPLIT_LEN", "256"))
+            if os.environ.get("DBLINK_LINK_SPLIT", "1") != "0" else 0
+        )
+        self._split_grid = int(os.environ.get("DBLINK_LINK_SPLIT_GRID", "256"))
+        # a block per listed record pays while such records are a handful and
+        # the sweep is launch- and tail-bound; at 1M records thousands are
+        # listed per sweep and the split path measured 5.7 ms slower than the
+        # wave kernel (BENCH.md), so it stops where the heavy sampler starts
+        self._split_max_records = int(
+            os.environ.get("DBLINK_LINK_SPLIT_MAX_RECORDS", "50000"))
+        self._split_cnt = torch.zeros(1, dtype=torch.int32, device=device)
+        self._split_list = torch.empty(0, dtype=torch.int32, device=device)
+        # k >= 2 (entity, attribute) pairs are classified once per sweep and
+        # the hash / merge value kernels run a wave per listed pair from a
+        # static grid; DBLINK_VALUE_LISTS=0 keeps the self-selecting walk
+        # over every pair (A/B; draws are bitwise identical)
+        self._vlists = os.environ.get("DBLINK_VALUE_LISTS", "1") != "0"
+        self._vlist_grid = int(os.environ.get("DBLINK_VALUE_LIST_GRID", "2048"))
+        self._vlist_cnt = torch.zeros(2, dtype=torch.int32, device=device)
+        self._vlist = torch.empty(0, dtype=torch.int32, device=device)
         self._value_stats = None
         if os.environ.get("DBLINK_VALUE_STATS", "") == "1":
             self._value_stats = torch.zeros(8, dtype=torch.int64, device=device)
@@ -476,8 +501,9 @@ class GpuEngine(CpuEngine):
 
     def _zero_counters(self, E):
         """One fill for everything the fused sweep accumulates into: the
-        log-likelihood partials, the summary counts, the per-entity record
-        counts and kobs live in one block (typed views of it)."""
+        log-likelihood partials, the summary counts, the link split list's
+        counter, the value pair-list counters, the per-entity record counts and kobs live in one block
+        (typed views of it)."""
         if self._zero_E == E:
             self._zero_blk.zero_()
             return
@@ -485,11 +511,15 @@ class GpuEngine(CpuEngine):
         n_ll, n_c = 2 * self._loglik_buf.numel(), 2 * self._counts.numel()
         # int32 words in front of the per-entity counters, which start on a
         # 16-byte boundary (scan_excl's vector loads)
-        head = -(-(n_ll + n_c) // 4) * 4
+        # (the link split list's counter and the two value pair-list
+        # counters are the last three words of that head)
+        head = -(-(n_ll + n_c + 3) // 4) * 4
         blk = torch.zeros(head + E + E * A, dtype=torch.int32, device=self.device)
         self._zero_blk = blk
         self._loglik_buf = blk[:n_ll].view(torch.float64)
         self._counts = blk[n_ll:n_ll + n_c].view(torch.int64)
+        self._split_cnt = blk[n_ll + n_c:n_ll + n_c + 1]
+        self._vlist_cnt = blk[n_ll + n_c + 1:n_ll + n_c + 3]
         self._ent_cnt = blk[head:head + E]
         self._kobs = blk[head + E:]
         self._zero_E = E
@@ -819,12 +849,19 @@ class GpuEngine(CpuEngine):
                 # 10k records across three kernels leaves the chip idle
                 # (~150 waves total) and costs more than it saves
                 mode_mask = torch.empty(0, dtype=torch.uint8, device=dev)
-            self.C.link_update(
+            split_len = self._split_len if R < self._split_max_records else 0
+            if split_len > 0:
+                if self._split_list.numel() != R:
+                    self._split_list = torch.empty(R, dtype=torch.int32, device=dev)
+                if not fused:  # the fused sweep's single fill covers the counter
+                    self._split_cnt.zero_()
+            self.C.link_update_split(
                 gs.rec_values, gs.rec_dist, gs.rec_gid, gs.rec_part,
                 cand_lo, cand_hi, postings, gs.ent_values,
                 ent_ptr, m.log_norm, m.voff, m.csr_row_ptr, m.csr_col, m.csr_sim,
                 m.attr_const, seed, it, rec_ent_new, gs.rec_ent, self._err,
                 mode_mask, ctrl, self._pair_a1, self._pair_a2,
+                self._split_list, self._split_cnt, split_len, self._split_grid,
             )
             if heavy_th > 0:
                 self.C.link_update_heavy(
@@ -867,7 +904,14 @@ class GpuEngine(CpuEngine):
             # A/B debugging aid: every pair on the wave path, no self-selection
             pair_wave = torch.arange(E * A, device=dev, dtype=torch.int64)
             kobs = torch.empty(0, dtype=torch.int32, device=dev)
-        self.C.value_update(
+        vlists = self._vlists and kobs.numel() > 0 and not flags.sequential
+        if vlists:
+            if self._vlist.numel() != E * A:
+                self._vlist = torch.empty(E * A, dtype=torch.int32, device=dev)
+            if not fused:  # the fused sweep's single fill covers the counters
+                self._vlist_cnt.zero_()
+        none32 = self._split_list[:0]
+        self.C.value_update_lists(
             gs.rec_values, gs.rec_dist, gs.rec_file, ent_rec_ptr, ent_rec_idx,
             gs.ent_values, m.theta, m.phi, m.log_phi, m.norm_lin, m.log_norm,
             m.voff, m.csr_row_ptr, m.csr_col, m.csr_sim, m.phi_prob, m.phi_alias,
@@ -876,6 +920,8 @@ class GpuEngine(CpuEngine):
             1 if flags.sequential else 0, seed, it, self._ent_id_base, self._err,
             pair_wave, self._empty_i64, self._empty_i64,
             m.csr_excl, m.csr_rawsum, m.z1, ctrl, kobs,
+            self._vlist if vlists else none32,
+            self._vlist_cnt if vlists else none32, self._vlist_grid,
         )
 
         self._mark("value", graph_safe)

@@ -79,6 +79,20 @@ void link_update(torch::Tensor rec_values, torch::Tensor rec_dist,
                  torch::Tensor rec_ent_in, torch::Tensor error_count,
                  torch::Tensor small_mask, torch::Tensor ctrl,
                  torch::Tensor pair_a1, torch::Tensor pair_a2);
+void link_update_split(torch::Tensor rec_values, torch::Tensor rec_dist,
+                       torch::Tensor rec_gid, torch::Tensor rec_part,
+                       torch::Tensor cand_lo, torch::Tensor cand_hi,
+                       torch::Tensor postings, torch::Tensor ent_values,
+                       torch::Tensor ent_ptr, torch::Tensor log_norm,
+                       torch::Tensor voff, torch::Tensor csr_row_ptr,
+                       torch::Tensor csr_col, torch::Tensor csr_sim,
+                       torch::Tensor attr_const, int64_t seed, int64_t iteration,
+                       torch::Tensor rec_ent_out, torch::Tensor rec_ent_in,
+                       torch::Tensor error_count, torch::Tensor small_mask,
+                       torch::Tensor ctrl, torch::Tensor pair_a1,
+                       torch::Tensor pair_a2, torch::Tensor split_list,
+                       torch::Tensor split_count, int64_t split_len,
+                       int64_t split_grid);
 void postings_hist(torch::Tensor ent_part, torch::Tensor ent_values,
                    torch::Tensor pair_a1, torch::Tensor pair_a2,
                    torch::Tensor pair_v2, int64_t Vmax, torch::Tensor counts);
@@ -140,6 +154,23 @@ void value_update(torch::Tensor rec_values, torch::Tensor rec_dist,
                   torch::Tensor k1_pairs, torch::Tensor csr_excl,
                   torch::Tensor csr_rawsum, torch::Tensor z1, torch::Tensor ctrl,
                   torch::Tensor kobs);
+void value_update_lists(torch::Tensor rec_values, torch::Tensor rec_dist,
+                  torch::Tensor rec_file, torch::Tensor ent_rec_ptr,
+                  torch::Tensor ent_rec_idx, torch::Tensor ent_values,
+                  torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
+                  torch::Tensor norm_lin, torch::Tensor log_norm, torch::Tensor voff,
+                  torch::Tensor csr_row_ptr, torch::Tensor csr_col,
+                  torch::Tensor csr_sim, torch::Tensor phi_prob,
+                  torch::Tensor phi_alias, torch::Tensor pow_prob,
+                  torch::Tensor pow_alias, torch::Tensor pow_off,
+                  torch::Tensor log_pow_total, torch::Tensor attr_const, int64_t Kc,
+                  int64_t collapsed, int64_t sequential, int64_t seed,
+                  int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
+                  torch::Tensor wave_pairs, torch::Tensor base_pairs,
+                  torch::Tensor k1_pairs, torch::Tensor csr_excl,
+                  torch::Tensor csr_rawsum, torch::Tensor z1, torch::Tensor ctrl,
+                  torch::Tensor kobs, torch::Tensor pair_lists,
+                        torch::Tensor list_count, int64_t list_grid);
 void distortion_update(torch::Tensor rec_values, torch::Tensor rec_dist,
                        torch::Tensor rec_file, torch::Tensor rec_gid,
                        torch::Tensor rec_ent, torch::Tensor ent_values,
@@ -236,9 +267,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("strs"), py::arg("lens"), py::arg("threshold"), py::arg("max_sim"),
         py::arg("prefix_scale"));
   m.def("link_update", &dblink::link_update, "K3/K4/K5 fused link update");
+  m.def("link_update_split", &dblink::link_update_split,
+        "link update with long candidate lists on the block-per-record path");
   m.def("link_update_dense", &dblink::link_update_dense,
         "dense link update (PCG-II / Gibbs-Sequential)");
   m.def("value_update", &dblink::value_update, "K6 entity-value update");
+  m.def("value_update_lists", &dblink::value_update_lists,
+        "K6 entity-value update, k >= 2 pairs routed by device-side lists");
   m.def("distortion_update", &dblink::distortion_update, "K7 distortion resample");
   m.def("summary_loglik", &dblink::summary_loglik, "K8 log-likelihood reduction");
   m.def("kd_descent", &dblink::kd_descent, "K9a KD-tree partition reassignment");

@@ -3,6 +3,8 @@
 // Kernel inventory (K-numbers as in STATUS.md "§2.2 / §2.4 kernels"):
 //   K4+K5  link_update{,_small,_heavy}_kernel — wave / thread / hierarchical
 //              A* link draw, one shared candidate-scoring core (link_* below)
+//          link_update_split_kernel — a block per wave-path record whose
+//              base list is long, served from a device-side list
 //          link_update_dense_kernel — PCG-II / Gibbs-Sequential partition scan
 //   K6     value_base_draw (k=0), value_update_k1, _kd1, _kd2,
 //              value_update_kernel_t<VMODE> (LDS hash / union merge), _seq
@@ -55,6 +57,11 @@ constexpr uint32_t PH_LINK = 1, PH_DIST = 2, PH_VALG = 3, PH_VALM = 4,
 // ---------------------------------------------------------------------------
 constexpr int SIMH_CAP = 512;  // staged entries per wave (4 KB key+value)
 
+// NT = threads that fill one table together: WAVE (a wave, lane = its lane id)
+// or a whole block (lane = threadIdx.x; the caller adds a __syncthreads()
+// before the first lookup). Every branch below is uniform across the NT
+// threads, so the block form's barrier is reached by all of them.
+template <int NT>
 __device__ inline void simh_stage(
     int32_t* kh, float* vh, int lane, const int64_t* __restrict__ csr_row_ptr,
     const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
@@ -77,9 +84,10 @@ __device__ inline void simh_stage(
     while ((1 << lg) < 2 * len) ++lg;
     if (lg > 9 || cursor + (1 << lg) > SIMH_CAP) continue;  // stays global
     const int sz = 1 << lg, base = cursor;
-    for (int i = lane; i < sz; i += WAVE) kh[base + i] = -1;
+    for (int i = lane; i < sz; i += NT) kh[base + i] = -1;
     // wave-lockstep: the CAS claims below see the -1 fill of this wave
-    for (int i = lane; i < len; i += WAVE) {
+    if (NT > WAVE) __syncthreads();
+    for (int i = lane; i < len; i += NT) {
       const int32_t y = csr_col[lo + i];
       int h = (int)(((uint32_t)y * 2654435761u) >> (32 - lg));
       for (;;) {
@@ -273,7 +281,10 @@ __global__ void link_update_kernel(
     uint64_t seed, uint32_t iteration, const int64_t* __restrict__ ctrl,
     int64_t* __restrict__ rec_ent_out,       // [R]
     const int64_t* __restrict__ rec_ent_in,  // [R]
-    int* __restrict__ error_count, int simh_on) {
+    int* __restrict__ error_count, int simh_on,
+    int64_t split_len,                       // 0 = no split path
+    int32_t* __restrict__ split_list,        // [R] records left to the split kernel
+    int* __restrict__ split_count) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wid = threadIdx.x / WAVE;
   __shared__ int32_t simh_k_s[4][SIMH_CAP];  // launcher uses WPB == 4
@@ -289,6 +300,12 @@ __global__ void link_update_kernel(
       link_classify(rec_values, rec_dist, attr_const, r, A);
   const LinkBase base = link_select_base(cand_lo, cand_hi, pair_a1, pair_a2,
                                          NP, rec_part, ent_ptr, r, A, nd_mask);
+  // a list longer than split_len is not scanned by one wave: the record goes
+  // on the list that link_update_split_kernel serves in the next launch
+  if (split_len > 0 && base.n > split_len) {
+    if (lane == 0) split_list[atomicAdd(split_count, 1)] = (int32_t)r;
+    return;
+  }
 
   const uint64_t gid = (uint64_t)rec_gid[r];
   // stage this record's od-attr sim rows into LDS when the scan is long
@@ -297,7 +314,7 @@ __global__ void link_update_kernel(
   int32_t* simh_k = simh_k_s[wid];
   float* simh_v = simh_v_s[wid];
   if (simh_on && od_mask && base.n * __popc(od_mask) >= 32)
-    simh_stage(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
+    simh_stage<WAVE>(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, od_mask, logpk, offpk);
   const auto sim = [&](int a, int64_t row, int32_t y) {
     return simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr, csr_col,
@@ -361,6 +378,115 @@ __global__ void link_update_small_kernel(
     if (logw + g > best_score) { best_score = logw + g; best_e = e; }
   }
   rec_ent_out[r] = link_winner_or_keep(best_e, rec_ent_in, r, error_count);
+}
+
+// Block-per-record link update for the few records whose base list is long
+// (a partition-sized scan, or a low-cardinality posting range). On the wave
+// kernel such a record is ~40 dependent rounds of gathers on one wave while
+// the chip idles; here LINK_SPLIT_WAVES waves stride the same list, the od
+// sim rows are staged once per block, and the argmax is combined in LDS.
+//
+// The winner must be the wave kernel's, f32 ties included (two candidates
+// of equal log-weight tie whenever their uniforms round to the same float,
+// which happens at partition-sized lists). There, with i the position in the
+// base list, lane i % 64 keeps the first maximum it meets under strict '>',
+// i.e. the lowest i / 64, and wave_argmax's shuffle tree keeps, among equal
+// scores, the lane whose id is lowest read with its 6 bits REVERSED (the
+// last step pits even lanes against odd ones and the even side stays, the
+// step before decides bit 1, ...). So the total order is: higher score, then
+// lower bit-reversed i % 64, then lower i / 64. Thread t scans positions
+// t, t + 1024, ... in ascending order (same i % 64, ascending i / 64), and
+// link_split_better() below carries the position through both reductions.
+constexpr int LINK_SPLIT_WAVES = 16;
+constexpr int LINK_SPLIT_THREADS = LINK_SPLIT_WAVES * WAVE;
+
+DBL_D bool link_split_better(float s_a, int64_t i_a, float s_b, int64_t i_b) {
+  if (s_a != s_b) return s_a > s_b;
+  const uint32_t la = __brev((uint32_t)(i_a & 63)) >> 26;
+  const uint32_t lb = __brev((uint32_t)(i_b & 63)) >> 26;
+  if (la != lb) return la < lb;
+  return i_a < i_b;
+}
+
+__global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
+    const int32_t* __restrict__ split_list, const int* __restrict__ split_count,
+    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
+    const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
+    const int64_t* __restrict__ cand_lo, const int64_t* __restrict__ cand_hi,
+    const int32_t* __restrict__ postings, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ ent_ptr, const float* __restrict__ log_norm,
+    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
+    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
+    const uint8_t* __restrict__ attr_const, const int32_t* __restrict__ pair_a1,
+    const int32_t* __restrict__ pair_a2, int NP, int A, uint64_t seed,
+    uint32_t iteration, const int64_t* __restrict__ ctrl,
+    int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
+    int* __restrict__ error_count, int simh_on) {
+  __shared__ int32_t simh_k[SIMH_CAP];
+  __shared__ float simh_v[SIMH_CAP];
+  __shared__ float red_s[LINK_SPLIT_WAVES];
+  __shared__ int64_t red_i[LINK_SPLIT_WAVES];
+  __shared__ long long red_e[LINK_SPLIT_WAVES];
+  const int tid = threadIdx.x;
+  const int lane = tid & (WAVE - 1);
+  const int wid = tid / WAVE;
+  ctrl_override(ctrl, seed, iteration);
+  // the list was completed by the previous launch; a list longer than the
+  // (static) grid is served by the stride
+  const int n_listed = *split_count;
+  for (int j = blockIdx.x; j < n_listed; j += gridDim.x) {
+    const int64_t r = split_list[j];
+    const auto [nd_mask, od_mask] =
+        link_classify(rec_values, rec_dist, attr_const, r, A);
+    const LinkBase base = link_select_base(cand_lo, cand_hi, pair_a1, pair_a2,
+                                           NP, rec_part, ent_ptr, r, A, nd_mask);
+    const uint64_t gid = (uint64_t)rec_gid[r];
+    uint64_t logpk = 0, offpk = 0;
+    if (simh_on && od_mask)
+      simh_stage<LINK_SPLIT_THREADS>(simh_k, simh_v, tid, csr_row_ptr, csr_col,
+                                     csr_sim, voff, rec_values, r, A, od_mask,
+                                     logpk, offpk);
+    __syncthreads();  // table complete (and red_* of the last record read)
+    const auto sim = [&](int a, int64_t row, int32_t y) {
+      return simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr, csr_col,
+                         csr_sim, row, y);
+    };
+    float best_score = -INFINITY;
+    long long best_e = -1;
+    int64_t best_i = INT64_MAX;
+    for (int64_t i = tid; i < base.n; i += LINK_SPLIT_THREADS) {
+      int32_t e = base.postings ? postings[base.lo + i] : (int32_t)(base.lo + i);
+      if (!link_matches(ent_values, rec_values, e, r, A, base.check_mask)) continue;
+      const float logw =
+          link_logw(ent_values, rec_values, log_norm, voff, e, r, A, od_mask, sim);
+      const float g = gumbel_from_uniform(
+          philox_uniform(seed, iteration, PH_LINK, gid, (uint32_t)e));
+      if (logw + g > best_score) { best_score = logw + g; best_e = e; best_i = i; }
+    }
+#pragma unroll
+    for (int off = WAVE / 2; off > 0; off >>= 1) {
+      const float other_s = __shfl_down(best_score, off);
+      const long long other_e = __shfl_down(best_e, off);
+      const int64_t other_i = __shfl_down(best_i, off);
+      if (lane + off < WAVE && other_e >= 0 &&
+          (best_e < 0 || link_split_better(other_s, other_i, best_score, best_i))) {
+        best_score = other_s; best_e = other_e; best_i = other_i;
+      }
+    }
+    if (lane == 0) { red_s[wid] = best_score; red_i[wid] = best_i; red_e[wid] = best_e; }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < LINK_SPLIT_WAVES; ++w)
+        if (red_e[w] >= 0 &&
+            (best_e < 0 || link_split_better(red_s[w], red_i[w], best_score, best_i))) {
+          best_score = red_s[w]; best_i = red_i[w]; best_e = red_e[w];
+        }
+      rec_ent_out[r] = link_winner_or_keep(best_e, rec_ent_in, r, error_count);
+    }
+    // no barrier here: the next record's staging touches simh_* only, which
+    // every wave has finished probing, and red_* is rewritten behind the
+    // barrier above, which thread 0 reaches after this combine
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -454,7 +580,7 @@ __global__ void link_update_heavy_kernel(
   int32_t* simh_k = simh_k_s[wid];
   float* simh_v = simh_v_s[wid];
   if (simh_on && od_mask)
-    simh_stage(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
+    simh_stage<WAVE>(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, od_mask, logpk, offpk);
   const auto sim = [&](int a, int64_t row, int32_t y) {
     return simh_lookup(simh_k, simh_v, logpk, offpk, a, csr_row_ptr, csr_col,
@@ -661,7 +787,7 @@ __global__ void link_update_dense_kernel(
   int32_t* simh_k = simh_k_s[wid];
   float* simh_v = simh_v_s[wid];
   if (simh_on && st_mask && (e1 - e0) * __popc(st_mask) >= 32)
-    simh_stage(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
+    simh_stage<WAVE>(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, st_mask, logpk, offpk);
 
   float best_score = -INFINITY;
@@ -764,6 +890,12 @@ struct ValueArgs {
   //                sum_units, sum_kobs, rare_pairs, merge_entries}
   unsigned long long* stats;
   int vchunk;  // 1 = chunked hash-accumulate dense path (DBLINK_VCHUNK)
+  // list mode (kobs mode only, or null): the k >= 2 pairs of the hash and the
+  // merge kernel, classified once per sweep by value_update_kd1_kernel. One
+  // [E*A] buffer holds both lists: hash pairs fill it from the front, merge
+  // pairs from the back (a pair is on at most one list).
+  int32_t* pair_lists;
+  int* list_count;  // [2] = {hash pairs, merge pairs}, zeroed by the caller
 };
 
 // --- shared draw core --------------------------------------------------------
@@ -788,6 +920,87 @@ DBL_D ValuePair value_pair_of(const ValueArgs& args, int64_t pair) {
   const int V = (int)(args.voff[a + 1] - v0);
   const uint64_t elem = (args.ent_id_base + (uint64_t)e) * 32u + (uint64_t)a;
   return {e, a, v0, V, elem, is_const};
+}
+
+// --- which kernel owns a k >= 2 pair ----------------------------------------
+// Exactly one kernel writes each pair. The predicates exist once, here: the
+// wave kernels apply them inside value_update_pair, and list mode applies
+// them once per pair and sweep in value_route (thread-per-pair), so that the
+// wave kernels only ever see their own pairs.
+constexpr int VOWN_HASH = 0, VOWN_MERGE = 1, VOWN_KD1 = 2, VOWN_KD2 = 3;
+
+// Settled without perturbation weights: the non-collapsed copy of a held
+// (non-distorted) value, or a constant attribute's non-collapsed base draw.
+DBL_D bool value_settles_early(const ValueArgs& args, bool is_const, bool has_nondist) {
+  return !args.collapsed && (has_nondist || is_const);
+}
+
+// The sim rows of the pair's units overflow the per-wave LDS hash.
+DBL_D bool value_is_dense(int64_t total_entries) {
+  return total_entries > (HASH_CAP * 3) / 4;
+}
+
+// One (value, file) group with cached k-tables: value_update_kd1_kernel's.
+DBL_D bool value_goes_kd1(const ValueArgs& args, bool is_const, bool gover, int d,
+                          int k_obs) {
+  return args.kobs != nullptr && args.tab_excl != nullptr && !is_const && !gover &&
+         d == 1 && k_obs <= args.ktab_max && k_obs <= args.Kc;
+}
+
+// Two distinct VALUES with cached (k, m) tables: value_update_kd2_kernel's.
+DBL_D bool value_goes_kd2(const ValueArgs& args, bool is_const, bool gover, int d,
+                          int k_obs, int32_t x0, int32_t x1) {
+  return args.kobs != nullptr && args.tab2_excl != nullptr && !is_const && !gover &&
+         d == 2 && k_obs <= args.k2tab_max && x0 != x1;
+}
+
+DBL_D int64_t value_row_entries(const ValueArgs& args, const ValuePair& p, int32_t x) {
+  return p.is_const ? 1
+                    : args.csr_row_ptr[p.v0 + x + 1] - args.csr_row_ptr[p.v0 + x];
+}
+
+// The owner of pair p (k_obs >= 2) and its first group, by one thread. Groups
+// are the distinct (value, file) of the observed records in record order, as
+// value_update_pair collects them into gbuf: a record opens a group unless an
+// earlier record holds its (value, file), found by re-scanning (k is a
+// handful, so no per-thread array). A new group beyond VAL_DMAX sets gover,
+// and the units become the k_obs records themselves.
+struct ValueRoute { int owner; int32_t x, f; };
+
+DBL_D ValueRoute value_route(const ValueArgs& args, const ValuePair& p, int k_obs) {
+  const int a = p.a;
+  const int64_t r_lo = args.ent_rec_ptr[p.e], r_hi = args.ent_rec_ptr[p.e + 1];
+  bool has_nondist = false, gover = false;
+  int d = 0;
+  int32_t x0 = -1, f0 = -1, x1 = -1;
+  int64_t group_entries = 0, record_entries = 0;
+  for (int64_t i = r_lo; i < r_hi; ++i) {
+    const int64_t r = args.ent_rec_idx[i];
+    const int32_t x = args.rec_values[r * args.A + a];
+    if (x < 0) continue;
+    if (!args.collapsed && !args.rec_dist[r * args.A + a]) has_nondist = true;
+    const int32_t f = args.collapsed ? args.rec_file[r] : 0;
+    const int64_t len = value_row_entries(args, p, x);
+    record_entries += len;
+    if (gover) continue;
+    bool seen = false;
+    for (int64_t j = r_lo; j < i && !seen; ++j) {
+      const int64_t rr = args.ent_rec_idx[j];
+      seen = args.rec_values[rr * args.A + a] == x &&
+             (args.collapsed ? args.rec_file[rr] : 0) == f;
+    }
+    if (seen) continue;
+    if (d == VAL_DMAX) { gover = true; continue; }
+    if (d == 0) { x0 = x; f0 = f; }
+    if (d == 1) x1 = x;
+    ++d;
+    group_entries += len;
+  }
+  if (value_settles_early(args, p.is_const, has_nondist)) return {VOWN_HASH, x0, f0};
+  if (value_goes_kd1(args, p.is_const, gover, d, k_obs)) return {VOWN_KD1, x0, f0};
+  if (value_goes_kd2(args, p.is_const, gover, d, k_obs, x0, x1)) return {VOWN_KD2, x0, f0};
+  return {value_is_dense(gover ? record_entries : group_entries) ? VOWN_MERGE : VOWN_HASH,
+          x0, f0};
 }
 
 // The table kernels' four uniforms: mixture test, CDF target (both f64: the
@@ -1024,27 +1237,42 @@ __global__ void value_update_kd1_kernel(ValueArgs args) {
   if (i >= args.n_pairs) return;
   const int64_t pair = i;
   const int k = args.kobs[pair];
-  if (k < 2 || k > args.ktab_max) return;
+  if (k < 2) return;
   const ValuePair p = value_pair_of(args, pair);
-  if (p.is_const) return;
   const int64_t e = p.e, v0 = p.v0;
   const int a = p.a;
-
-  // all observed linked records must share one (value, file); any
-  // non-distorted observed record (non-collapsed) defers to the wave path
-  const int64_t r_lo = args.ent_rec_ptr[e], r_hi = args.ent_rec_ptr[e + 1];
   int32_t x = -1, f = -1;
-  for (int64_t j = r_lo; j < r_hi; ++j) {
-    const int64_t r = args.ent_rec_idx[j];
-    const int32_t xx = args.rec_values[r * args.A + a];
-    if (xx < 0) continue;
-    if (!args.collapsed && !args.rec_dist[r * args.A + a]) return;
-    const int32_t ff = args.collapsed ? args.rec_file[r] : 0;
-    if (x < 0) { x = xx; f = ff; }
-    else if (xx != x || ff != f) return;  // multi-group: wave path
+  if (args.list_count != nullptr) {
+    // list mode: this thread already has to scan the pair's records, so it
+    // is where every k >= 2 pair is classified, once per sweep. Pairs of
+    // the wave kernels go on their lists (order arbitrary: each pair reads
+    // records and writes its own ent_values slot only); kd2 self-selects.
+    const ValueRoute rt = value_route(args, p, k);
+    if (rt.owner == VOWN_HASH)
+      args.pair_lists[atomicAdd(&args.list_count[0], 1)] = (int32_t)pair;
+    else if (rt.owner == VOWN_MERGE)
+      args.pair_lists[args.n_pairs - 1 - atomicAdd(&args.list_count[1], 1)] =
+          (int32_t)pair;
+    if (rt.owner != VOWN_KD1) return;
+    x = rt.x;
+    f = rt.f;
+  } else {
+    if (k > args.ktab_max || p.is_const) return;
+    // all observed linked records must share one (value, file); any
+    // non-distorted observed record (non-collapsed) defers to the wave path
+    const int64_t r_lo = args.ent_rec_ptr[e], r_hi = args.ent_rec_ptr[e + 1];
+    for (int64_t j = r_lo; j < r_hi; ++j) {
+      const int64_t r = args.ent_rec_idx[j];
+      const int32_t xx = args.rec_values[r * args.A + a];
+      if (xx < 0) continue;
+      if (!args.collapsed && !args.rec_dist[r * args.A + a]) return;
+      const int32_t ff = args.collapsed ? args.rec_file[r] : 0;
+      if (x < 0) { x = xx; f = ff; }
+      else if (xx != x || ff != f) return;  // multi-group: wave path
+    }
+    if (x < 0) return;
+    if (k > args.Kc) return;  // no cached power dist (rare path stays on wave)
   }
-  if (x < 0) return;
-  if (k > args.Kc) return;  // no cached power dist (rare path stays on wave)
 
   const ValueUniforms u = value_uniforms(args, p.elem);
 
@@ -1289,7 +1517,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   };
 
   // non-collapsed deterministic copy (GibbsUpdates.scala:619-630)
-  if (!args.collapsed && first_nondist >= 0) {
+  if (value_settles_early(args, false, first_nondist >= 0)) {
     if (lane == 0) args.ent_values[e * args.A + a] = first_nondist;
     return;
   }
@@ -1300,7 +1528,7 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
     return;
   }
 
-  if (!args.collapsed && is_const) {  // no perturbation for const non-collapsed
+  if (value_settles_early(args, is_const, false)) {  // no perturbation for const non-collapsed
     int v = base_draw(0xFFFF0000u);
     if (lane == 0) args.ent_values[e * args.A + a] = (int32_t)v;
     return;
@@ -1430,13 +1658,9 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
   // size the table (and its clear/scan cost) to the actual support
   int64_t total_entries = 0;
   for (int u = 0; u < n_units; ++u) {
-    const int32_t ux = unit_of(u).x;
-    if (is_const)
-      total_entries += 1;
-    else
-      total_entries += args.csr_row_ptr[v0 + ux + 1] - args.csr_row_ptr[v0 + ux];
+    total_entries += value_row_entries(args, p, unit_of(u).x);
   }
-  const bool dense = total_entries > (HASH_CAP * 3) / 4;
+  const bool dense = value_is_dense(total_entries);
   if (VMODE == 1 && dense) return;   // the merge kernel's pair
   if (VMODE == 2 && !dense) return;  // the hash kernel's pair
   int tsize = 64;
@@ -1454,12 +1678,9 @@ __device__ void value_update_pair(const ValueArgs& args, int64_t pair, int lane,
 
   // single-(value, file) pairs with cached k-tables are the kd1 kernel's
   // (kobs mode only; explicit pair lists keep the full path)
-  if (args.kobs != nullptr && args.tab_excl != nullptr && !is_const &&
-      !gover && d == 1 && k_obs <= args.ktab_max && k_obs <= args.Kc)
-    return;
+  if (value_goes_kd1(args, is_const, gover, d, k_obs)) return;
   // two distinct VALUES with cached (k, m) tables: the kd2 kernel's
-  if (args.kobs != nullptr && args.tab2_excl != nullptr && !is_const &&
-      !gover && d == 2 && k_obs <= args.k2tab_max && gbuf[0] != gbuf[1])
+  if (d >= 2 && value_goes_kd2(args, is_const, gover, d, k_obs, gbuf[0], gbuf[1]))
     return;
 
   double W = 0.0;            // total perturbation weight
@@ -1661,6 +1882,17 @@ value_update_kernel_t(ValueArgs args) {
     value_update_pair<VMODE>(args, args.pair_list[widx], lane, h_key[wave],
                              h_val[wave], g_buf[wave], g_lo[wave], g_n[wave],
                              g_se[wave]);
+  } else if (args.list_count != nullptr) {
+    // list mode (VMODE 1 or 2): one wave per listed pair of this kernel, a
+    // static grid striding over a list whose length is read from the device
+    const bool merge = VMODE == 2;
+    const int64_t n = args.list_count[merge ? 1 : 0];
+    const int64_t n_waves = (int64_t)gridDim.x * WAVES_PER_BLOCK_VAL;
+    for (int64_t j = widx; j < n; j += n_waves) {
+      const int64_t pair = args.pair_lists[merge ? args.n_pairs - 1 - j : j];
+      value_update_pair<VMODE>(args, pair, lane, h_key[wave], h_val[wave],
+                               g_buf[wave], g_lo[wave], g_n[wave], g_se[wave]);
+    }
   } else {
     // kobs self-selection: each wave examines VAL_STRIDE consecutive pairs
     // and runs the (rare) k >= 2 ones serially
@@ -3024,7 +3256,11 @@ static LinkArgs make_link_args(
   return a;
 }
 
-void link_update(
+// split_len > 0 takes records whose base list is longer off the wave kernel:
+// it appends them to split_list ([R] int32, count in split_count[0], zeroed
+// by the caller) and link_update_split_kernel serves the list from a static
+// grid of split_grid blocks, so the launch pair is graph-safe.
+void link_update_split(
     torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
     torch::Tensor rec_part, torch::Tensor cand_lo, torch::Tensor cand_hi,
     torch::Tensor postings, torch::Tensor ent_values, torch::Tensor ent_ptr,
@@ -3033,7 +3269,8 @@ void link_update(
     int64_t seed, int64_t iteration, torch::Tensor rec_ent_out,
     torch::Tensor rec_ent_in, torch::Tensor error_count,
     torch::Tensor small_mask, torch::Tensor ctrl, torch::Tensor pair_a1,
-    torch::Tensor pair_a2) {
+    torch::Tensor pair_a2, torch::Tensor split_list, torch::Tensor split_count,
+    int64_t split_len, int64_t split_grid) {
   const LinkArgs L = make_link_args(
       rec_values, rec_dist, rec_gid, rec_part, ent_values, ent_ptr, log_norm,
       voff, csr_row_ptr, csr_col, csr_sim, attr_const, seed, iteration, ctrl,
@@ -3046,6 +3283,21 @@ void link_update(
   const int32_t* a1 = pair_a1.data_ptr<int32_t>();
   const int32_t* a2 = pair_a2.data_ptr<int32_t>();
   constexpr int WPB = 4;
+  int32_t* list_ptr = nullptr;
+  int* count_ptr = nullptr;
+  if (split_len > 0) {
+    CHECK_GPU(split_list);
+    CHECK_GPU(split_count);
+    TORCH_CHECK(split_list.scalar_type() == torch::kInt32 &&
+                    split_count.scalar_type() == torch::kInt32,
+                "split_list and split_count must be int32");
+    TORCH_CHECK(split_list.numel() >= L.R && split_count.numel() >= 1,
+                "split_list holds R records, split_count one counter");
+    TORCH_CHECK(L.R <= INT32_MAX, "split list indexes records with int32");
+    TORCH_CHECK(split_grid >= 1 && split_grid <= 65535, "split_grid out of range");
+    list_ptr = split_list.data_ptr<int32_t>();
+    count_ptr = split_count.data_ptr<int>();
+  }
   const bool split = small_mask.numel() > 0;
   const uint8_t* mask_ptr = split ? small_mask.data_ptr<uint8_t>() : nullptr;
   hipLaunchKernelGGL(link_update_kernel, dim3((unsigned)wave_grid(L.R, WPB)),
@@ -3054,7 +3306,17 @@ void link_update(
                      post, L.ent_values, L.ent_ptr, L.log_norm, L.voff,
                      L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, a1, a2,
                      NP, mask_ptr, L.R, L.A, L.seed, L.iteration, L.ctrl,
-                     L.rec_ent_out, L.rec_ent_in, L.error_count, L.simh_on);
+                     L.rec_ent_out, L.rec_ent_in, L.error_count, L.simh_on,
+                     split_len, list_ptr, count_ptr);
+  if (split_len > 0)
+    hipLaunchKernelGGL(link_update_split_kernel, dim3((unsigned)split_grid),
+                       dim3(LINK_SPLIT_THREADS), 0,
+                       at::cuda::getCurrentCUDAStream(), list_ptr, count_ptr,
+                       L.rec_values, L.rec_dist, L.rec_gid, L.rec_part, lo, hi,
+                       post, L.ent_values, L.ent_ptr, L.log_norm, L.voff,
+                       L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, a1,
+                       a2, NP, L.A, L.seed, L.iteration, L.ctrl, L.rec_ent_out,
+                       L.rec_ent_in, L.error_count, L.simh_on);
   if (split)
     hipLaunchKernelGGL(link_update_small_kernel,
                        dim3((unsigned)((L.R + 255) / 256)), dim3(256), 0,
@@ -3064,6 +3326,23 @@ void link_update(
                        L.csr_row_ptr, L.csr_col, L.csr_sim, L.attr_const, a1,
                        a2, NP, L.A, L.seed, L.iteration, L.ctrl, L.rec_ent_out,
                        L.rec_ent_in, L.error_count);
+}
+
+void link_update(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
+    torch::Tensor rec_part, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor postings, torch::Tensor ent_values, torch::Tensor ent_ptr,
+    torch::Tensor log_norm, torch::Tensor voff, torch::Tensor csr_row_ptr,
+    torch::Tensor csr_col, torch::Tensor csr_sim, torch::Tensor attr_const,
+    int64_t seed, int64_t iteration, torch::Tensor rec_ent_out,
+    torch::Tensor rec_ent_in, torch::Tensor error_count,
+    torch::Tensor small_mask, torch::Tensor ctrl, torch::Tensor pair_a1,
+    torch::Tensor pair_a2) {
+  link_update_split(rec_values, rec_dist, rec_gid, rec_part, cand_lo, cand_hi,
+                    postings, ent_values, ent_ptr, log_norm, voff, csr_row_ptr,
+                    csr_col, csr_sim, attr_const, seed, iteration, rec_ent_out,
+                    rec_ent_in, error_count, small_mask, ctrl, pair_a1, pair_a2,
+                    torch::Tensor(), torch::Tensor(), 0, 0);
 }
 
 void postings_hist(torch::Tensor ent_part, torch::Tensor ent_values,
@@ -3340,6 +3619,8 @@ static ValueArgs make_value_args(
   a.ctrl = nullptr;
   a.kobs = nullptr;
   a.pair_list = nullptr;
+  a.pair_lists = nullptr;
+  a.list_count = nullptr;
   a.stats = g_value_stats;
   {
     const char* e = std::getenv("DBLINK_VCHUNK");
@@ -3390,7 +3671,12 @@ static ValueArgs make_value_args(
   return a;
 }
 
-void value_update(
+// pair_lists ([E*A] int32) and list_count ([2] int32, zeroed by the caller)
+// switch the kobs mode to list mode: value_update_kd1_kernel classifies every
+// k >= 2 pair once and the hash and merge kernels run one wave per listed
+// pair from a static grid of at most list_grid blocks. Empty tensors keep the
+// self-selecting kobs mode.
+void value_update_lists(
     torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_file,
     torch::Tensor ent_rec_ptr, torch::Tensor ent_rec_idx, torch::Tensor ent_values,
     torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
@@ -3402,7 +3688,8 @@ void value_update(
     int64_t seed, int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
     torch::Tensor wave_pairs, torch::Tensor base_pairs, torch::Tensor k1_pairs,
     torch::Tensor csr_excl, torch::Tensor csr_rawsum, torch::Tensor z1,
-    torch::Tensor ctrl, torch::Tensor kobs) {
+    torch::Tensor ctrl, torch::Tensor kobs, torch::Tensor pair_lists,
+    torch::Tensor list_count, int64_t list_grid) {
   ValueArgs args = make_value_args(
       rec_values, rec_dist, rec_file, ent_rec_ptr, ent_rec_idx, ent_values, theta,
       phi, log_phi, norm_lin, log_norm, voff, csr_row_ptr, csr_col, csr_sim,
@@ -3436,12 +3723,30 @@ void value_update(
     // k=1, k>=2 table kd1/kd2, k>=2 hash, k>=2 union-merge)
     args.kobs = kobs.data_ptr<int32_t>();
     args.n_pairs = kobs.numel();
+    const bool lists = list_count.numel() > 0;
+    if (lists) {
+      CHECK_GPU(pair_lists);
+      CHECK_GPU(list_count);
+      TORCH_CHECK(pair_lists.scalar_type() == torch::kInt32 &&
+                      list_count.scalar_type() == torch::kInt32,
+                  "pair_lists and list_count must be int32");
+      TORCH_CHECK(pair_lists.numel() >= args.n_pairs && list_count.numel() >= 2,
+                  "pair_lists holds E*A pairs, list_count two counters");
+      TORCH_CHECK(args.n_pairs <= INT32_MAX, "pair lists index pairs with int32");
+      TORCH_CHECK(list_grid >= 1, "list_grid must be positive");
+      args.pair_lists = pair_lists.data_ptr<int32_t>();
+      args.list_count = list_count.data_ptr<int>();
+    }
     launch_threads(value_base_draw_kernel);
     launch_threads(value_update_k1_kernel);
-    if (args.tab_excl != nullptr) launch_threads(value_update_kd1_kernel);
+    // in list mode kd1 also classifies, so it runs without k-tables too
+    if (lists || args.tab_excl != nullptr) launch_threads(value_update_kd1_kernel);
     if (args.tab2_excl != nullptr)
       launch_waves(value_update_kd2_kernel, (args.n_pairs + 7) / 8);
-    const int64_t n_waves = (args.n_pairs + VAL_STRIDE - 1) / VAL_STRIDE;
+    // list mode: a wave per listed pair, at most list_grid blocks that stride
+    const int64_t n_waves =
+        lists ? std::min(args.n_pairs, list_grid * WAVES_PER_BLOCK_VAL)
+              : (args.n_pairs + VAL_STRIDE - 1) / VAL_STRIDE;
     launch_waves(value_update_kernel_t<1>, n_waves);
     launch_waves(value_update_kernel_t<2>, n_waves);
     return;
@@ -3455,6 +3760,28 @@ void value_update(
   if (use_list(base_pairs)) launch_threads(value_base_draw_kernel);
   if (use_list(k1_pairs)) launch_threads(value_update_k1_kernel);
   if (use_list(wave_pairs)) launch_waves(value_update_kernel_t<0>, args.n_pairs);
+}
+
+void value_update(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_file,
+    torch::Tensor ent_rec_ptr, torch::Tensor ent_rec_idx, torch::Tensor ent_values,
+    torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
+    torch::Tensor norm_lin, torch::Tensor log_norm, torch::Tensor voff,
+    torch::Tensor csr_row_ptr, torch::Tensor csr_col, torch::Tensor csr_sim,
+    torch::Tensor phi_prob, torch::Tensor phi_alias, torch::Tensor pow_prob,
+    torch::Tensor pow_alias, torch::Tensor pow_off, torch::Tensor log_pow_total,
+    torch::Tensor attr_const, int64_t Kc, int64_t collapsed, int64_t sequential,
+    int64_t seed, int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
+    torch::Tensor wave_pairs, torch::Tensor base_pairs, torch::Tensor k1_pairs,
+    torch::Tensor csr_excl, torch::Tensor csr_rawsum, torch::Tensor z1,
+    torch::Tensor ctrl, torch::Tensor kobs) {
+  value_update_lists(rec_values, rec_dist, rec_file, ent_rec_ptr, ent_rec_idx,
+                     ent_values, theta, phi, log_phi, norm_lin, log_norm, voff,
+                     csr_row_ptr, csr_col, csr_sim, phi_prob, phi_alias, pow_prob,
+                     pow_alias, pow_off, log_pow_total, attr_const, Kc, collapsed,
+                     sequential, seed, iteration, ent_id_base, error_count,
+                     wave_pairs, base_pairs, k1_pairs, csr_excl, csr_rawsum, z1,
+                     ctrl, kobs, torch::Tensor(), torch::Tensor(), 0);
 }
 
 void distortion_update(
