@@ -372,6 +372,18 @@ class GpuEngine(CpuEngine):
         # (kernels.hip "Sweep glue"); DBLINK_FUSED_GLUE=0 keeps the torch
         # expressions it replaces, as the A/B reference arm
         self._fused = os.environ.get("DBLINK_FUSED_GLUE", "1") != "0"
+        # launch merging inside the fused glue (A/B arms; results are
+        # bit-identical either way):
+        # DBLINK_INDEX_MERGE=0 keeps the index counters' fill and the
+        # stand-alone cand_ranges launch (default: the scan clears the
+        # counters, the scatter launch computes the ranges);
+        # DBLINK_VALUE_MERGE=0 keeps one launch per thread-per-pair value
+        # class (default: value_update_thread_kernel covers all three)
+        self._index_merge = os.environ.get("DBLINK_INDEX_MERGE", "1") != "0"
+        self._value_merge = os.environ.get("DBLINK_VALUE_MERGE", "1") != "0"
+        # True while _idx_counts is known to be all zero (left so by the
+        # clearing scan), so the next histogram needs no fill
+        self._idx_clean = False
         self._resort_cap = int(self.C.resort_max_parts())
         self._loglik_buf = torch.zeros(256, dtype=torch.float64, device=device)
         A, F = self.model.A, self.model.F
@@ -495,6 +507,7 @@ class GpuEngine(CpuEngine):
             self._idx_counts = torch.zeros(nk, dtype=torch.int32, device=self.device)
             self._idx_ptr = torch.zeros(nk + 1, dtype=torch.int64, device=self.device)
             self._idx_cursor = torch.empty(nk, dtype=torch.int32, device=self.device)
+            self._idx_clean = False
         elif zero:
             self._idx_counts.zero_()
         return nk
@@ -568,6 +581,7 @@ class GpuEngine(CpuEngine):
         inverted index (atomic adds, so stay-home and arrival contributions
         compose in any order)."""
         self._ensure_idx_buffers(zero=reset)
+        self._idx_clean = False
         vmax = max(self.model.Vmax, self._pair_vmax)
         self.C.postings_hist(ent_part, ent_values, self._pair_a1,
                              self._pair_a2, self._pair_v2, vmax,
@@ -767,18 +781,26 @@ class GpuEngine(CpuEngine):
             if nk <= (1 << 28):  # dense counters (1 GiB cap; always true in practice)
                 dense_idx = True
                 if not hist_pre:
-                    self._ensure_idx_buffers(zero=True)
+                    # no fill while the previous sweep's scan left them zero
+                    self._ensure_idx_buffers(zero=not self._idx_clean)
+                    self._idx_clean = False
                     self.C.postings_hist(gs.ent_part, gs.ent_values, self._pair_a1,
                                          self._pair_a2, self._pair_v2, vmax,
                                          self._idx_counts)
                 heavy_sort = self._heavy_active(R) or \
                     os.environ.get("DBLINK_FORCE_SORT", "") == "1"
+                index_merge = fused and self._index_merge
                 if fused:
                     # prefix and scatter cursor from one scan (one block while
-                    # the key space is small, the device scan above that)
+                    # the key space is small, the device scan above that),
+                    # which on a single rank also zeroes the counters for the
+                    # next sweep's histogram
+                    clear = index_merge and self.world_size <= 1
                     self.C.scan_excl(
                         self._idx_counts, self._idx_ptr,
-                        self._idx_cursor[:0] if heavy_sort else self._idx_cursor)
+                        self._idx_cursor[:0] if heavy_sort else self._idx_cursor,
+                        clear)
+                    self._idx_clean = clear
                 else:
                     torch.cumsum(self._idx_counts, 0, dtype=torch.int64,
                                  out=self._idx_ptr[1:])
@@ -801,15 +823,23 @@ class GpuEngine(CpuEngine):
                     if not fused:
                         self._idx_cursor.copy_(self._idx_ptr[:-1])
                     postings = torch.empty(T * E, dtype=torch.int32, device=dev)
-                    self.C.postings_scatter(gs.ent_part, gs.ent_values,
-                                            self._pair_a1, self._pair_a2,
-                                            self._pair_v2, vmax,
-                                            self._idx_cursor, postings)
                 cand_lo = torch.empty((R, T), dtype=torch.int64, device=dev)
                 cand_hi = torch.empty((R, T), dtype=torch.int64, device=dev)
-                self.C.cand_ranges(gs.rec_part, gs.rec_values, self._pair_a1,
-                                   self._pair_a2, self._pair_v2, self._idx_ptr,
-                                   vmax, cand_lo, cand_hi)
+                if index_merge and not heavy_sort:
+                    # scatter and ranges both hang off the scan: one launch
+                    self.C.postings_scatter_ranges(
+                        gs.ent_part, gs.ent_values, gs.rec_part, gs.rec_values,
+                        self._pair_a1, self._pair_a2, self._pair_v2, vmax,
+                        self._idx_cursor, self._idx_ptr, postings, cand_lo, cand_hi)
+                else:
+                    if not heavy_sort:
+                        self.C.postings_scatter(gs.ent_part, gs.ent_values,
+                                                self._pair_a1, self._pair_a2,
+                                                self._pair_v2, vmax,
+                                                self._idx_cursor, postings)
+                    self.C.cand_ranges(gs.rec_part, gs.rec_values, self._pair_a1,
+                                       self._pair_a2, self._pair_v2, self._idx_ptr,
+                                       vmax, cand_lo, cand_hi)
             else:  # degenerate key space: radix sort + batched searchsorted
                 keys = torch.empty(T * E, dtype=torch.int64, device=dev)
                 qkeys = torch.empty(R * T, dtype=torch.int64, device=dev)
@@ -911,7 +941,9 @@ class GpuEngine(CpuEngine):
             if not fused:  # the fused sweep's single fill covers the counters
                 self._vlist_cnt.zero_()
         none32 = self._split_list[:0]
-        self.C.value_update_lists(
+        value_update = (self.C.value_update_merged if self._value_merge
+                        else self.C.value_update_lists)
+        value_update(
             gs.rec_values, gs.rec_dist, gs.rec_file, ent_rec_ptr, ent_rec_idx,
             gs.ent_values, m.theta, m.phi, m.log_phi, m.norm_lin, m.log_norm,
             m.voff, m.csr_row_ptr, m.csr_col, m.csr_sim, m.phi_prob, m.phi_alias,

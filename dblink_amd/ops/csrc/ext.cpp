@@ -171,6 +171,23 @@ void value_update_lists(torch::Tensor rec_values, torch::Tensor rec_dist,
                   torch::Tensor csr_rawsum, torch::Tensor z1, torch::Tensor ctrl,
                   torch::Tensor kobs, torch::Tensor pair_lists,
                         torch::Tensor list_count, int64_t list_grid);
+void value_update_merged(torch::Tensor rec_values, torch::Tensor rec_dist,
+                  torch::Tensor rec_file, torch::Tensor ent_rec_ptr,
+                  torch::Tensor ent_rec_idx, torch::Tensor ent_values,
+                  torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
+                  torch::Tensor norm_lin, torch::Tensor log_norm, torch::Tensor voff,
+                  torch::Tensor csr_row_ptr, torch::Tensor csr_col,
+                  torch::Tensor csr_sim, torch::Tensor phi_prob,
+                  torch::Tensor phi_alias, torch::Tensor pow_prob,
+                  torch::Tensor pow_alias, torch::Tensor pow_off,
+                  torch::Tensor log_pow_total, torch::Tensor attr_const, int64_t Kc,
+                  int64_t collapsed, int64_t sequential, int64_t seed,
+                  int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
+                  torch::Tensor wave_pairs, torch::Tensor base_pairs,
+                  torch::Tensor k1_pairs, torch::Tensor csr_excl,
+                  torch::Tensor csr_rawsum, torch::Tensor z1, torch::Tensor ctrl,
+                  torch::Tensor kobs, torch::Tensor pair_lists,
+                  torch::Tensor list_count, int64_t list_grid);
 void distortion_update(torch::Tensor rec_values, torch::Tensor rec_dist,
                        torch::Tensor rec_file, torch::Tensor rec_gid,
                        torch::Tensor rec_ent, torch::Tensor ent_values,
@@ -203,7 +220,15 @@ void scalar_score_bench(torch::Tensor rcode, torch::Tensor rbonus,
 void summary_counts(torch::Tensor rec_dist, torch::Tensor rec_file,
                     torch::Tensor ent_rec_ptr, int64_t E, torch::Tensor counts,
                     torch::Tensor loglik, torch::Tensor packed, torch::Tensor err);
-void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor);
+void postings_scatter_ranges(torch::Tensor ent_part, torch::Tensor ent_values,
+                             torch::Tensor rec_part, torch::Tensor rec_values,
+                             torch::Tensor pair_a1, torch::Tensor pair_a2,
+                             torch::Tensor pair_v2, int64_t Vmax,
+                             torch::Tensor cursor, torch::Tensor ptr,
+                             torch::Tensor postings, torch::Tensor cand_lo,
+                             torch::Tensor cand_hi);
+void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor,
+               bool clear);
 void ent_csr_build(torch::Tensor rec_ent_new, torch::Tensor rec_values,
                    torch::Tensor rec_ent, torch::Tensor ent_cnt,
                    torch::Tensor kobs, torch::Tensor ent_rec_ptr,
@@ -297,9 +322,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("summary_counts", &dblink::summary_counts,
         "fused summary counts + pack (+ the error count in the last slot)");
   m.def("scan_excl", &dblink::scan_excl,
-        "exclusive int32 -> int64 prefix with an optional int32 cursor copy");
+        "exclusive int32 -> int64 prefix with an optional int32 cursor copy; "
+        "clear=True leaves counts all zero",
+        py::arg("counts"), py::arg("ptr"), py::arg("cursor"),
+        py::arg("clear") = false);
+  m.def("postings_scatter_ranges", &dblink::postings_scatter_ranges,
+        "counting-sort index: posting scatter and candidate ranges, one launch");
   m.def("ent_csr_build", &dblink::ent_csr_build,
         "entity -> records CSR (stable order) + kobs + link store");
+  m.def("value_update_merged", &dblink::value_update_merged,
+        "value_update_lists with one launch for the thread-per-pair classes");
   m.def("resort_max_parts", &dblink::resort_max_parts,
         "partition-count cap of partition_resort");
   m.def("resort_hist_size", &dblink::resort_hist_size,

@@ -1137,16 +1137,20 @@ __device__ int dense_power_draw(const ValueArgs& args, int a, int k, uint64_t el
 
 // Thread-per-pair base draws for empty clusters (k_obs == 0): the base
 // distribution is phi for every variant (GibbsUpdates.scala:584-588).
+DBL_D void value_base_draw_pair(const ValueArgs& args, int64_t pair) {
+  const ValuePair p = value_pair_of(args, pair);
+  float u1, u2;
+  philox_uniform2(args.seed, args.iteration, PH_VALM, p.elem, 0xFFFF0000u, &u1, &u2);
+  args.ent_values[p.e * args.A + p.a] = (int32_t)value_base_alias(args, p, 0, u1, u2);
+}
+
 __global__ void value_base_draw_kernel(ValueArgs args) {
   ctrl_override(args.ctrl, args.seed, args.iteration);
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= args.n_pairs) return;
   const int64_t pair = args.pair_list ? args.pair_list[i] : i;
   if (args.kobs && args.kobs[pair] != 0) return;
-  const ValuePair p = value_pair_of(args, pair);
-  float u1, u2;
-  philox_uniform2(args.seed, args.iteration, PH_VALM, p.elem, 0xFFFF0000u, &u1, &u2);
-  args.ent_values[p.e * args.A + p.a] = (int32_t)value_base_alias(args, p, 0, u1, u2);
+  value_base_draw_pair(args, pair);
 }
 
 // Thread-per-pair value update for single-record clusters (k_obs == 1).
@@ -1156,12 +1160,7 @@ __global__ void value_base_draw_kernel(ValueArgs args) {
 // raw_w1[j] = phi(col)*norm(col)*(expsim-1), their exclusive row prefix and
 // row totals, a draw is: one Philox call, a mixture test, and one binary
 // search over the row prefix — O(log row) regardless of row size.
-__global__ void value_update_k1_kernel(ValueArgs args) {
-  ctrl_override(args.ctrl, args.seed, args.iteration);
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= args.n_pairs) return;
-  const int64_t pair = args.pair_list ? args.pair_list[i] : i;
-  if (args.kobs && args.kobs[pair] != 1) return;
+DBL_D void value_update_k1_pair(const ValueArgs& args, int64_t pair) {
   const ValuePair p = value_pair_of(args, pair);
   const int64_t e = p.e, v0 = p.v0;
   const int a = p.a;
@@ -1224,6 +1223,15 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
   args.ent_values[e * args.A + a] = (int32_t)v_new;
 }
 
+__global__ void value_update_k1_kernel(ValueArgs args) {
+  ctrl_override(args.ctrl, args.seed, args.iteration);
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= args.n_pairs) return;
+  const int64_t pair = args.pair_list ? args.pair_list[i] : i;
+  if (args.kobs && args.kobs[pair] != 1) return;
+  value_update_k1_pair(args, pair);
+}
+
 // Thread-per-pair value update for clusters whose observed linked records
 // all share ONE (value, file) — the dominant k >= 2 class (measured d~1.1-1.6
 // mean distinct values per pair at 1M/10M stationarity). The perturbation
@@ -1231,13 +1239,7 @@ __global__ void value_update_k1_kernel(ValueArgs args) {
 // (set_value_ktables), so a draw is one Philox call, the theta-dependent
 // self-power correction, a mixture test and one binary search — O(log row)
 // like the k = 1 kernel, replacing an O(k row) wave merge.
-__global__ void value_update_kd1_kernel(ValueArgs args) {
-  ctrl_override(args.ctrl, args.seed, args.iteration);
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= args.n_pairs) return;
-  const int64_t pair = i;
-  const int k = args.kobs[pair];
-  if (k < 2) return;
+DBL_D void value_update_kd1_pair(const ValueArgs& args, int64_t pair, int k) {
   const ValuePair p = value_pair_of(args, pair);
   const int64_t e = p.e, v0 = p.v0;
   const int a = p.a;
@@ -1305,6 +1307,34 @@ __global__ void value_update_kd1_kernel(ValueArgs args) {
                           args.csr_row_ptr[v0 + x], args.csr_row_ptr[v0 + x + 1], t);
   }
   args.ent_values[e * args.A + a] = (int32_t)v_new;
+}
+
+__global__ void value_update_kd1_kernel(ValueArgs args) {
+  ctrl_override(args.ctrl, args.seed, args.iteration);
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= args.n_pairs) return;
+  const int k = args.kobs[i];
+  if (k < 2) return;
+  value_update_kd1_pair(args, i, k);
+}
+
+// The three thread-per-pair kernels above as one launch in kobs mode: they
+// cover the same pairs and act on disjoint classes (k = 0, k = 1, k >= 2),
+// each writing only its own pair's ent_values word, so one thread reads
+// kobs[pair] once and takes its class's branch. `kd1` carries the launcher's
+// condition for the k >= 2 kernel.
+__global__ void value_update_thread_kernel(ValueArgs args, bool kd1) {
+  ctrl_override(args.ctrl, args.seed, args.iteration);
+  const int64_t pair = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (pair >= args.n_pairs) return;
+  const int k = args.kobs[pair];
+  if (k == 0) {
+    value_base_draw_pair(args, pair);
+  } else if (k == 1) {
+    value_update_k1_pair(args, pair);
+  } else if (k >= 2 && kd1) {
+    value_update_kd1_pair(args, pair, k);
+  }
 }
 
 // Wave-per-pair value update for clusters spanning exactly TWO distinct
@@ -2201,7 +2231,8 @@ __global__ __launch_bounds__(PB_THREADS) void postings_hist_kernel(
     if (h_key[i] >= 0) atomicAdd(&counts[h_key[i]], h_cnt[i]);
 }
 
-__global__ __launch_bounds__(PB_THREADS) void postings_scatter_kernel(
+// Scatter of block blockIdx.x's PB_THREADS (slot, entity) items.
+DBL_D void postings_scatter_block(
     const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
     const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
     const int32_t* __restrict__ pair_v2, int64_t E, int A, int NP, int64_t Vmax,
@@ -2244,6 +2275,15 @@ __global__ __launch_bounds__(PB_THREADS) void postings_scatter_kernel(
   if (my_slot >= 0) postings[h_base[my_slot] + my_rank] = e_out;
 }
 
+__global__ __launch_bounds__(PB_THREADS) void postings_scatter_kernel(
+    const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, int64_t E, int A, int NP, int64_t Vmax,
+    int32_t* __restrict__ cursor, int32_t* __restrict__ postings) {
+  postings_scatter_block(ent_part, ent_values, pair_a1, pair_a2, pair_v2, E, A, NP,
+                         Vmax, cursor, postings);
+}
+
 // One thread per record: route each record to one of three link paths.
 //   mode 0 = wave scan (link_update_kernel)
 //   mode 1 = thread scan (link_update_small_kernel, short candidate list)
@@ -2280,13 +2320,14 @@ __global__ void classify_modes_kernel(
   mode[r] = m;
 }
 
-__global__ void cand_ranges_kernel(
+// Candidate range of (record, slot) item idx off the dense key prefix.
+DBL_D void cand_range_item(
     const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
     const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
     const int32_t* __restrict__ pair_v2, const int64_t* __restrict__ ptr,
     int64_t R, int A, int NP, int64_t Vmax,
-    int64_t* __restrict__ cand_lo, int64_t* __restrict__ cand_hi) {  // [R * T]
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t* __restrict__ cand_lo, int64_t* __restrict__ cand_hi,  // [R * T]
+    int64_t idx) {
   const int T = A + NP;
   if (idx >= R * T) return;
   const int64_t r = idx / T;
@@ -2307,6 +2348,38 @@ __global__ void cand_ranges_kernel(
   const int64_t key = ((int64_t)rec_part[r] * T + t) * Vmax + v;
   cand_lo[idx] = ptr[key];
   cand_hi[idx] = ptr[key + 1];
+}
+
+__global__ void cand_ranges_kernel(
+    const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, const int64_t* __restrict__ ptr,
+    int64_t R, int A, int NP, int64_t Vmax,
+    int64_t* __restrict__ cand_lo, int64_t* __restrict__ cand_hi) {
+  cand_range_item(rec_part, rec_values, pair_a1, pair_a2, pair_v2, ptr, R, A, NP,
+                  Vmax, cand_lo, cand_hi,
+                  (int64_t)blockIdx.x * blockDim.x + threadIdx.x);
+}
+
+// The posting scatter and the candidate ranges both need only the scanned
+// prefix, so they share a launch: the first n_scatter blocks scatter, the
+// rest take PB_THREADS (record, slot) items each. No block waits for another.
+__global__ __launch_bounds__(PB_THREADS) void postings_scatter_ranges_kernel(
+    const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, const int64_t* __restrict__ ptr,
+    int64_t E, int64_t R, int A, int NP, int64_t Vmax, unsigned n_scatter,
+    int32_t* __restrict__ cursor, int32_t* __restrict__ postings,
+    int64_t* __restrict__ cand_lo, int64_t* __restrict__ cand_hi) {
+  if (blockIdx.x < n_scatter) {
+    postings_scatter_block(ent_part, ent_values, pair_a1, pair_a2, pair_v2, E, A,
+                           NP, Vmax, cursor, postings);
+  } else {
+    cand_range_item(rec_part, rec_values, pair_a1, pair_a2, pair_v2, ptr, R, A, NP,
+                    Vmax, cand_lo, cand_hi,
+                    (int64_t)(blockIdx.x - n_scatter) * PB_THREADS + threadIdx.x);
+  }
 }
 
 // Summary counts in one pass: per-record distortion histogram + per
@@ -2556,11 +2629,25 @@ DBL_D void scan_load4(const int32_t* __restrict__ counts, int64_t i0, int64_t n,
   }
 }
 
+// Zeros over one thread's four counters (same access shape as scan_load4).
+DBL_D void scan_clear4(int32_t* __restrict__ counts, int64_t i0, int64_t n, bool vec) {
+  if (vec && i0 + 4 <= n) {
+    *reinterpret_cast<int4*>(counts + i0) = make_int4(0, 0, 0, 0);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (i0 + j < n) counts[i0 + j] = 0;
+  }
+}
+
+// With `clear` the counters are zeroed once they have been scanned: the next
+// histogram accumulates into a clean buffer without a fill launch of its own.
 __global__ __launch_bounds__(GL_THREADS) void scan_excl_kernel(
-    const int32_t* __restrict__ counts, int64_t n,
+    int32_t* __restrict__ counts, int64_t n,
     int64_t* __restrict__ ptr,       // [n + 1]
     int32_t* __restrict__ cursor,    // [n] copy of ptr[:n], or null
-    bool vec) {                      // all three buffers 16-byte aligned
+    bool vec,                        // all three buffers 16-byte aligned
+    bool clear) {                    // store zeros back over counts
   __shared__ int64_t wave_tot[GL_WAVES];
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -2613,6 +2700,11 @@ __global__ __launch_bounds__(GL_THREADS) void scan_excl_kernel(
     __syncthreads();  // wave_tot is rewritten by the next tile
   }
   if (threadIdx.x == 0) ptr[n] = carry;
+  // every thread zeroes exactly the counters it loaded, after the last wait
+  // of the scan, so the stores only have to drain by the kernel's end
+  if (clear)
+    for (int64_t base = 0; base < n; base += TILE)
+      scan_clear4(counts, base + (int64_t)threadIdx.x * 4, n, vec);
 }
 
 // Count pass: records per entity, observed values per (entity, attribute),
@@ -3516,6 +3608,46 @@ void cand_ranges(torch::Tensor rec_part, torch::Tensor rec_values,
                      cand_lo.data_ptr<int64_t>(), cand_hi.data_ptr<int64_t>());
 }
 
+// postings_scatter and cand_ranges as one launch (same results as the pair).
+void postings_scatter_ranges(torch::Tensor ent_part, torch::Tensor ent_values,
+                             torch::Tensor rec_part, torch::Tensor rec_values,
+                             torch::Tensor pair_a1, torch::Tensor pair_a2,
+                             torch::Tensor pair_v2, int64_t Vmax,
+                             torch::Tensor cursor, torch::Tensor ptr,
+                             torch::Tensor postings, torch::Tensor cand_lo,
+                             torch::Tensor cand_hi) {
+  CHECK_GPU(ent_values);
+  CHECK_CONTIG(ent_values);
+  CHECK_CONTIG(rec_values);
+  CHECK_CONTIG(postings);
+  CHECK_CONTIG(cand_lo);
+  CHECK_CONTIG(cand_hi);
+  const int64_t E = ent_values.size(0), R = rec_values.size(0);
+  const int A = (int)ent_values.size(1);
+  const int NP = (int)pair_a1.numel();
+  const int64_t T = A + NP;
+  TORCH_CHECK(rec_values.size(1) == A && ent_part.numel() == E &&
+              rec_part.numel() == R && postings.numel() >= E * T &&
+              cand_lo.numel() == R * T && cand_hi.numel() == R * T &&
+              ptr.numel() == cursor.numel() + 1,
+              "postings_scatter_ranges: shape mismatch");
+  TORCH_CHECK(cursor.numel() <= INT32_MAX, "dense key space exceeds int32");
+  const int64_t n_scatter = (E * T + PB_THREADS - 1) / PB_THREADS;
+  const int64_t n_ranges = (R * T + PB_THREADS - 1) / PB_THREADS;
+  if (n_scatter + n_ranges == 0) return;
+  TORCH_CHECK(n_scatter + n_ranges <= INT32_MAX, "postings_scatter_ranges: grid too large");
+  hipLaunchKernelGGL(postings_scatter_ranges_kernel,
+                     dim3((unsigned)(n_scatter + n_ranges)), dim3(PB_THREADS), 0,
+                     at::cuda::getCurrentCUDAStream(),
+                     ent_part.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
+                     rec_part.data_ptr<int32_t>(), rec_values.data_ptr<int32_t>(),
+                     pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
+                     pair_v2.data_ptr<int32_t>(), ptr.data_ptr<int64_t>(), E, R, A,
+                     NP, Vmax, (unsigned)n_scatter, cursor.data_ptr<int32_t>(),
+                     postings.data_ptr<int32_t>(), cand_lo.data_ptr<int64_t>(),
+                     cand_hi.data_ptr<int64_t>());
+}
+
 void link_update_dense(
     torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
     torch::Tensor rec_part, torch::Tensor rec_file, torch::Tensor ent_values,
@@ -3676,7 +3808,7 @@ static ValueArgs make_value_args(
 // k >= 2 pair once and the hash and merge kernels run one wave per listed
 // pair from a static grid of at most list_grid blocks. Empty tensors keep the
 // self-selecting kobs mode.
-void value_update_lists(
+static void value_update_run(
     torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_file,
     torch::Tensor ent_rec_ptr, torch::Tensor ent_rec_idx, torch::Tensor ent_values,
     torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
@@ -3689,7 +3821,7 @@ void value_update_lists(
     torch::Tensor wave_pairs, torch::Tensor base_pairs, torch::Tensor k1_pairs,
     torch::Tensor csr_excl, torch::Tensor csr_rawsum, torch::Tensor z1,
     torch::Tensor ctrl, torch::Tensor kobs, torch::Tensor pair_lists,
-    torch::Tensor list_count, int64_t list_grid) {
+    torch::Tensor list_count, int64_t list_grid, bool thread_merge) {
   ValueArgs args = make_value_args(
       rec_values, rec_dist, rec_file, ent_rec_ptr, ent_rec_idx, ent_values, theta,
       phi, log_phi, norm_lin, log_norm, voff, csr_row_ptr, csr_col, csr_sim,
@@ -3737,10 +3869,17 @@ void value_update_lists(
       args.pair_lists = pair_lists.data_ptr<int32_t>();
       args.list_count = list_count.data_ptr<int>();
     }
-    launch_threads(value_base_draw_kernel);
-    launch_threads(value_update_k1_kernel);
     // in list mode kd1 also classifies, so it runs without k-tables too
-    if (lists || args.tab_excl != nullptr) launch_threads(value_update_kd1_kernel);
+    const bool kd1 = lists || args.tab_excl != nullptr;
+    if (thread_merge) {
+      hipLaunchKernelGGL(value_update_thread_kernel,
+                         dim3((unsigned)((args.n_pairs + 255) / 256)), dim3(256), 0,
+                         stream, args, kd1);
+    } else {
+      launch_threads(value_base_draw_kernel);
+      launch_threads(value_update_k1_kernel);
+      if (kd1) launch_threads(value_update_kd1_kernel);
+    }
     if (args.tab2_excl != nullptr)
       launch_waves(value_update_kd2_kernel, (args.n_pairs + 7) / 8);
     // list mode: a wave per listed pair, at most list_grid blocks that stride
@@ -3760,6 +3899,54 @@ void value_update_lists(
   if (use_list(base_pairs)) launch_threads(value_base_draw_kernel);
   if (use_list(k1_pairs)) launch_threads(value_update_k1_kernel);
   if (use_list(wave_pairs)) launch_waves(value_update_kernel_t<0>, args.n_pairs);
+}
+
+void value_update_lists(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_file,
+    torch::Tensor ent_rec_ptr, torch::Tensor ent_rec_idx, torch::Tensor ent_values,
+    torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
+    torch::Tensor norm_lin, torch::Tensor log_norm, torch::Tensor voff,
+    torch::Tensor csr_row_ptr, torch::Tensor csr_col, torch::Tensor csr_sim,
+    torch::Tensor phi_prob, torch::Tensor phi_alias, torch::Tensor pow_prob,
+    torch::Tensor pow_alias, torch::Tensor pow_off, torch::Tensor log_pow_total,
+    torch::Tensor attr_const, int64_t Kc, int64_t collapsed, int64_t sequential,
+    int64_t seed, int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
+    torch::Tensor wave_pairs, torch::Tensor base_pairs, torch::Tensor k1_pairs,
+    torch::Tensor csr_excl, torch::Tensor csr_rawsum, torch::Tensor z1,
+    torch::Tensor ctrl, torch::Tensor kobs, torch::Tensor pair_lists,
+    torch::Tensor list_count, int64_t list_grid) {
+  value_update_run(rec_values, rec_dist, rec_file, ent_rec_ptr, ent_rec_idx, ent_values,
+                   theta, phi, log_phi, norm_lin, log_norm, voff, csr_row_ptr,
+                   csr_col, csr_sim, phi_prob, phi_alias, pow_prob, pow_alias,
+                   pow_off, log_pow_total, attr_const, Kc, collapsed, sequential,
+                   seed, iteration, ent_id_base, error_count, wave_pairs,
+                   base_pairs, k1_pairs, csr_excl, csr_rawsum, z1, ctrl, kobs,
+                   pair_lists, list_count, list_grid, false);
+}
+
+// value_update_lists with the kobs mode's three thread-per-pair kernels as
+// one launch (value_update_thread_kernel); same draws.
+void value_update_merged(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_file,
+    torch::Tensor ent_rec_ptr, torch::Tensor ent_rec_idx, torch::Tensor ent_values,
+    torch::Tensor theta, torch::Tensor phi, torch::Tensor log_phi,
+    torch::Tensor norm_lin, torch::Tensor log_norm, torch::Tensor voff,
+    torch::Tensor csr_row_ptr, torch::Tensor csr_col, torch::Tensor csr_sim,
+    torch::Tensor phi_prob, torch::Tensor phi_alias, torch::Tensor pow_prob,
+    torch::Tensor pow_alias, torch::Tensor pow_off, torch::Tensor log_pow_total,
+    torch::Tensor attr_const, int64_t Kc, int64_t collapsed, int64_t sequential,
+    int64_t seed, int64_t iteration, int64_t ent_id_base, torch::Tensor error_count,
+    torch::Tensor wave_pairs, torch::Tensor base_pairs, torch::Tensor k1_pairs,
+    torch::Tensor csr_excl, torch::Tensor csr_rawsum, torch::Tensor z1,
+    torch::Tensor ctrl, torch::Tensor kobs, torch::Tensor pair_lists,
+    torch::Tensor list_count, int64_t list_grid) {
+  value_update_run(rec_values, rec_dist, rec_file, ent_rec_ptr, ent_rec_idx, ent_values,
+                   theta, phi, log_phi, norm_lin, log_norm, voff, csr_row_ptr,
+                   csr_col, csr_sim, phi_prob, phi_alias, pow_prob, pow_alias,
+                   pow_off, log_pow_total, attr_const, Kc, collapsed, sequential,
+                   seed, iteration, ent_id_base, error_count, wave_pairs,
+                   base_pairs, k1_pairs, csr_excl, csr_rawsum, z1, ctrl, kobs,
+                   pair_lists, list_count, list_grid, true);
 }
 
 void value_update(
@@ -3895,8 +4082,10 @@ void summary_counts(torch::Tensor rec_dist, torch::Tensor rec_file,
 
 // Exclusive prefix of int32 counts [n] into ptr [n + 1] (int64), with an
 // optional int32 cursor [n] = ptr[:n]: one block up to SCAN_SINGLE_MAX
-// counters, cumsum (+ copy) above.
-void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor) {
+// counters, cumsum (+ copy) above. With `clear`, counts is all zero on
+// return (inside the one-block scan; by a fill after cumsum above it).
+void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor,
+               bool clear) {
   CHECK_GPU(counts);
   CHECK_CONTIG(counts);
   CHECK_CONTIG(ptr);
@@ -3918,13 +4107,15 @@ void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor) {
     hipLaunchKernelGGL(scan_excl_kernel, dim3(1), dim3(GL_THREADS), 0,
                        at::cuda::getCurrentCUDAStream(),
                        counts.data_ptr<int32_t>(), n, ptr.data_ptr<int64_t>(),
-                       with_cursor ? cursor.data_ptr<int32_t>() : nullptr, vec);
+                       with_cursor ? cursor.data_ptr<int32_t>() : nullptr, vec,
+                       clear);
     return;
   }
   ptr.narrow(0, 0, 1).zero_();
   auto tail = ptr.narrow(0, 1, n);
   at::cumsum_out(tail, counts, 0, torch::kInt64);
   if (with_cursor) cursor.copy_(ptr.narrow(0, 0, n));
+  if (clear) counts.zero_();
 }
 
 // Entity -> records CSR in stable order, the kobs counts and the store of
@@ -3956,7 +4147,7 @@ void ent_csr_build(torch::Tensor rec_ent_new, torch::Tensor rec_values,
                        rec_values.data_ptr<int32_t>(), R, A,
                        rec_ent.numel() ? rec_ent.data_ptr<int64_t>() : nullptr,
                        ent_cnt.data_ptr<int32_t>(), kobs.data_ptr<int32_t>());
-  scan_excl(ent_cnt, ent_rec_ptr, ent_cnt.narrow(0, 0, 0));  // no cursor
+  scan_excl(ent_cnt, ent_rec_ptr, ent_cnt.narrow(0, 0, 0), false);  // no cursor
   if (R == 0) return;
   hipLaunchKernelGGL(csr_scatter_kernel, rgrid, dim3(256), 0, stream,
                      rec_ent_new.data_ptr<int64_t>(),
@@ -4018,7 +4209,7 @@ void partition_resort(
                      node_a.data_ptr<int32_t>(), node_b.data_ptr<int32_t>(),
                      rset.data_ptr<int32_t>(), E, A, (int)P, n_tiles,
                      ent_part.data_ptr<int32_t>(), hist.data_ptr<int32_t>());
-  scan_excl(hist, tile_base, hist.narrow(0, 0, 0));  // no cursor
+  scan_excl(hist, tile_base, hist.narrow(0, 0, 0), false);  // no cursor
   hipLaunchKernelGGL(resort_scatter_kernel, dim3((unsigned)n_tiles),
                      dim3(GL_THREADS), 0, stream, ent_part.data_ptr<int32_t>(),
                      ent_values.data_ptr<int32_t>(), tile_base.data_ptr<int64_t>(),
