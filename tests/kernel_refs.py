@@ -1,6 +1,7 @@
 """Plain numpy / fp64 references shared by ``test_gpu_link_index``,
-``test_gpu_dense_seq`` and ``test_kernel_refs`` (which holds them to the
-per-record oracle of ``cpu_engine`` without a GPU).
+``test_gpu_dense_seq``, ``test_gpu_value_dist``, ``test_gpu_distortion`` and
+``test_kernel_refs`` (which holds them to the per-record oracle of
+``cpu_engine`` and to known-answer vectors without a GPU).
 
 Nothing here touches a device or the native extension: the formulas are
 written from the update rules (GibbsUpdates.scala line references at each
@@ -178,6 +179,74 @@ def seq_value_probs(ia, xs_dist):
         for x in xs_dist:
             w *= index.sim_norms * _expsim_row(index, x, vs)
     return w / w.sum()
+
+
+def value_probs(ia, theta_a, recs, collapsed):
+    """The value conditional over the whole domain, in PRODUCT form
+    (GibbsUpdates.scala:576-646): P(v) ~ b(v) prod_i F_i(v). The kernels and
+    the CPU oracle draw from the equivalent mixture of the base distribution
+    and a perturbation on the union of the similarity rows; nothing of that
+    (no Z_k, no ``- 1``, no support set) appears here.
+
+    ``recs`` lists ``(x, file)`` of the observed linked records (k of them),
+    ``theta_a`` is theta[a, :]. b(v) = phi(v) norm(v)^k for a non-constant
+    attribute with k > 0, else phi(v). F_i(v) = expsim(x_i, v) (1 off the
+    truncated index, 1 everywhere for a constant attribute); collapsed adds
+    [v == x_i] (1 / theta[f_i] - 1) / (phi(x_i) norm(x_i)) to it, without the
+    norm for a constant attribute. Non-collapsed takes every record as
+    distorted and ignores theta, which leaves phi for a constant attribute."""
+    index = ia.index
+    phi = index.probs.astype(np.float64)
+    k = len(recs)
+    w = phi.copy()
+    if not ia.is_constant and k > 0:
+        w *= index.sim_norms.astype(np.float64) ** k
+    vs = np.arange(index.num_values)
+    for x, f in recs:
+        x = int(x)
+        fac = np.ones(len(vs)) if ia.is_constant else _expsim_row(index, x, vs)
+        if collapsed:
+            mass = phi[x] if ia.is_constant else phi[x] * float(index.sim_norms[x])
+            fac[x] += (1.0 / float(theta_a[f]) - 1.0) / mass
+        w *= fac
+    return w / w.sum()
+
+
+# ---- Philox with the GPU keying -----------------------------------------------------
+
+_M32 = np.uint64(0xFFFFFFFF)
+
+
+def philox4x32(seed, c0, c1, c2, c3):
+    """Philox4x32-10 (Salmon et al. 2011) as ``common.h`` keys it: key = low
+    and high word of ``seed``, counter = the four words, nothing else folded
+    into the key. Counter words broadcast; returns the four output words as
+    uint32 arrays."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0 = np.uint64(seed & 0xFFFFFFFF)
+    k1 = np.uint64(seed >> 32)
+    x = [np.asarray(c, dtype=np.uint64) & _M32 for c in np.broadcast_arrays(c0, c1, c2, c3)]
+    m0, m1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+    w0, w1 = np.uint64(0x9E3779B9), np.uint64(0xBB67AE85)
+    s32 = np.uint64(32)
+    for _ in range(10):
+        p0 = x[0] * m0            # 32 x 32 bits: fits uint64
+        p1 = x[2] * m1
+        x = [(p1 >> s32) ^ x[1] ^ k0, p1 & _M32, (p0 >> s32) ^ x[3] ^ k1, p0 & _M32]
+        k0 = (k0 + w0) & _M32
+        k1 = (k1 + w1) & _M32
+    return tuple(c.astype(np.uint32) for c in x)
+
+
+def gpu_uniform(seed, iteration, phase, elem, draw, word=0):
+    """fp64 value (x + 0.5) 2^-32 of output word ``word`` of the Philox call
+    behind ``philox_uniform`` / ``philox_uniform2`` / ``value_uniforms``:
+    counter = (elem low, elem high, iteration ^ (phase << 24), draw). The
+    kernels round the same word to f32 where they hold it as a float."""
+    elem = np.asarray(elem, dtype=np.uint64)
+    c2 = (int(iteration) ^ (int(phase) << 24)) & 0xFFFFFFFF
+    out = philox4x32(seed, elem & _M32, elem >> np.uint64(32), c2, int(draw) & 0xFFFFFFFF)
+    return (out[word].astype(np.float64) + 0.5) * 2.0 ** -32
 
 
 # ---- comparison ---------------------------------------------------------------------
