@@ -337,3 +337,253 @@ def shared_most_probable_clusters_fast(table):
     members = uniq_rids[best_codes[order]]
     return [set(members[bounds[i]:bounds[i + 1]].tolist())
             for i in range(len(bounds) - 1)]
+
+
+# ---- posterior pairwise link probabilities ----------------------------------
+
+MAX_PAIR_IDS = 2**31 - 1  # rank codes a < b must fit 31 bits of a pair key
+DEFAULT_CHUNK_PAIRS = 1 << 24
+PAIR_PROB_FILE = "pairwise-link-probabilities.csv"
+
+
+def _check_id_count(n):
+    if n > MAX_PAIR_IDS:
+        raise ValueError(
+            f"the chain holds {n} distinct record ids; pairwise link counts "
+            f"pack two id ranks into one 64-bit key and support at most "
+            f"{MAX_PAIR_IDS}")
+
+
+def _chain_rank_codes(table):
+    """Flatten the chain -> (uniq_ids, codes, offsets, S): the distinct
+    member ids in Python string order, each member's rank among them (int32)
+    and the int64 offsets of the cluster instances in ``codes``."""
+    import pyarrow as pa
+
+    col = table["linkageStructure"].combine_chunks()
+    if isinstance(col, pa.ChunkedArray):
+        col = col.combine_chunks()
+    clusters = col.flatten()
+    offsets = np.asarray(clusters.offsets).astype(np.int64)
+    members = clusters.flatten()
+    if isinstance(members, pa.ChunkedArray):
+        members = members.combine_chunks()
+    enc = members.dictionary_encode()
+    ids = enc.dictionary.to_pylist()
+    _check_id_count(len(ids))
+    # re-rank the dictionary codes by the sorted id strings, so that code
+    # order is the canonical output order
+    order = sorted(range(len(ids)), key=ids.__getitem__)
+    rank = np.empty(len(ids), dtype=np.int32)
+    rank[order] = np.arange(len(ids), dtype=np.int32)
+    uniq_ids = np.empty(len(ids), dtype=object)
+    uniq_ids[:] = [ids[i] for i in order]
+    codes = rank[np.asarray(enc.indices)] if len(ids) else np.empty(0, np.int32)
+    S = len(np.unique(np.asarray(table["iteration"].to_numpy())))
+    return uniq_ids, np.ascontiguousarray(codes, dtype=np.int32), offsets, S
+
+
+def _pairs_per_cluster(offsets):
+    s = np.diff(offsets)
+    return s * (s - 1) // 2
+
+
+def _pair_chunks(pair_ptr, chunk_pairs):
+    """Cluster ranges [c0, c1) of at most ``chunk_pairs`` pairs each; a
+    single cluster above that goes alone."""
+    C = len(pair_ptr) - 1
+    c0 = 0
+    while c0 < C:
+        c1 = int(np.searchsorted(pair_ptr, pair_ptr[c0] + chunk_pairs,
+                                 side="right")) - 1
+        c1 = min(max(c1, c0 + 1), C)
+        yield c0, c1
+        c0 = c1
+
+
+def _tri_decode(t):
+    """Pair index t -> (i, j), i < j, t = j (j - 1) / 2 + i: an fp64 root,
+    then an integer fix-up (the same decode as pair_counts.hip)."""
+    j = ((1.0 + np.sqrt(1.0 + 8.0 * t.astype(np.float64))) * 0.5).astype(np.int64)
+    np.maximum(j, 1, out=j)
+    while True:
+        high = j * (j - 1) // 2 > t
+        low = (j + 1) * j // 2 <= t
+        if not (high.any() or low.any()):
+            break
+        j = j - high + low
+    return t - j * (j - 1) // 2, j
+
+
+def _pair_keys_numpy(codes, offsets, pair_ptr, c0, c1):
+    """The (a << 32 | b) key, a < b, of every member pair of clusters
+    [c0, c1); a pair of equal codes (a duplicated member) is skipped."""
+    n_pairs = np.diff(pair_ptr[c0:c1 + 1])
+    cl = np.repeat(np.arange(c0, c1, dtype=np.int64), n_pairs)
+    t = np.arange(pair_ptr[c0], pair_ptr[c1], dtype=np.int64) - pair_ptr[cl]
+    i, j = _tri_decode(t)
+    base = offsets[cl]
+    x = codes[base + i].astype(np.int64)
+    y = codes[base + j].astype(np.int64)
+    keep = x != y
+    x, y = x[keep], y[keep]
+    return (np.minimum(x, y) << np.int64(32)) | np.maximum(x, y)
+
+
+def _merge_key_counts(keys, counts):
+    """Distinct sorted keys and their summed counts."""
+    if len(keys) == 0:
+        return np.empty(0, np.int64), np.empty(0, np.int64)
+    order = np.argsort(keys, kind="stable")
+    keys, counts = keys[order], counts[order]
+    starts = np.flatnonzero(np.r_[True, keys[1:] != keys[:-1]])
+    return keys[starts], np.add.reduceat(counts, starts).astype(np.int64)
+
+
+def _pair_counts_numpy(codes, offsets, pair_ptr, chunk_pairs):
+    ks, cs = [], []
+    for c0, c1 in _pair_chunks(pair_ptr, chunk_pairs):
+        k, c = np.unique(_pair_keys_numpy(codes, offsets, pair_ptr, c0, c1),
+                         return_counts=True)
+        ks.append(k)
+        cs.append(c.astype(np.int64))
+    if not ks:
+        return np.empty(0, np.int64), np.empty(0, np.int64)
+    return _merge_key_counts(np.concatenate(ks), np.concatenate(cs))
+
+
+def _pair_counts_gpu(codes, offsets, pair_ptr, chunk_pairs, initial_capacity=None,
+                     after_add=None):
+    """Counts through the device hash table; ``after_add(table)`` is called
+    after every chunk (tests watch the table grow through it)."""
+    import torch
+
+    from ..ops import PairCountTable
+
+    kw = {} if initial_capacity is None else {"initial_capacity": initial_capacity}
+    tab = PairCountTable(device="cuda", **kw)
+    codes_d = torch.from_numpy(codes).to(tab.device)
+    for c0, c1 in _pair_chunks(pair_ptr, chunk_pairs):
+        lo, hi = int(offsets[c0]), int(offsets[c1])
+        off_d = torch.from_numpy(offsets[c0:c1 + 1] - lo).to(tab.device)
+        tab.add(codes_d[lo:hi], off_d, int(pair_ptr[c1] - pair_ptr[c0]))
+        if after_add is not None:
+            after_add(tab)
+    keys, counts = tab.finish()
+    return keys.cpu().numpy(), counts.cpu().numpy()
+
+
+def pair_counts_from_codes(codes, offsets, device=None, chunk_pairs=None, **gpu_kw):
+    """Sorted distinct pair keys ``(a << 32) | b`` (a < b) and their int64
+    counts over the clusters ``codes[offsets[c]:offsets[c + 1]]``.
+    ``device`` "cpu" / "cuda" forces the arm; None asks
+    ``ops.pair_counts_route``."""
+    from .. import ops
+
+    codes = np.ascontiguousarray(codes, dtype=np.int32)
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if len(codes) and (codes.min() < 0):
+        raise ValueError("member codes must be non-negative")
+    chunk_pairs = DEFAULT_CHUNK_PAIRS if chunk_pairs is None else int(chunk_pairs)
+    if chunk_pairs < 1:
+        raise ValueError("chunk_pairs must be positive")
+    pair_ptr = np.zeros(len(offsets), dtype=np.int64)
+    np.cumsum(_pairs_per_cluster(offsets), out=pair_ptr[1:])
+    if device is None:
+        cuda = False
+        if ops.have_pair_table():
+            import torch
+
+            cuda = torch.cuda.is_available()
+        route = ops.pair_counts_route(int(pair_ptr[-1]), cuda)
+    else:
+        kind = str(device).split(":")[0]
+        if kind not in ("cpu", "cuda"):
+            raise ValueError(f"device must be 'cpu', 'cuda' or None, not {device!r}")
+        route = "gpu" if kind == "cuda" else "numpy"
+    if route == "gpu":
+        return _pair_counts_gpu(codes, offsets, pair_ptr, chunk_pairs, **gpu_kw)
+    return _pair_counts_numpy(codes, offsets, pair_ptr, chunk_pairs)
+
+
+def pairwise_link_counts(table, device=None, chunk_pairs=None):
+    """Co-clustering counts of record pairs along the chain.
+
+    Returns ``(uniq_ids, a, b, count, S)``: the distinct record ids in
+    string order, the rank codes ``a < b`` into them of every pair that
+    shares a cluster at least once (sorted by ``(a, b)``), the number of
+    cluster instances holding both (int64) and the number of samples S
+    (distinct iterations). ``count / S`` is the posterior link probability.
+    """
+    uniq_ids, codes, offsets, S = _chain_rank_codes(table)
+    keys, count = pair_counts_from_codes(codes, offsets, device, chunk_pairs)
+    a = (keys >> np.int64(32)).astype(np.int64)
+    b = (keys & np.int64(0xFFFFFFFF)).astype(np.int64)
+    return uniq_ids, a, b, count, S
+
+
+def min_link_count(min_probability, S):
+    """Smallest integer count with ``count / S >= min_probability``. The
+    probability is read as the decimal number it prints as (0.1 is one
+    tenth), so the comparison is exact: 0.5 with S = 4 gives 2."""
+    from fractions import Fraction
+
+    p = float(min_probability)
+    if not 0.0 <= p <= 1.0:
+        raise ValueError("min_probability must lie in [0, 1]")
+    need = Fraction(repr(p)) * S
+    return -(-need.numerator // need.denominator)
+
+
+def pairwise_link_probabilities(table, min_probability=0.0, device=None):
+    """DataFrame (recordId1, recordId2, probability) of the pairs whose
+    posterior link probability is positive and at least ``min_probability``;
+    recordId1 < recordId2, rows sorted by (recordId1, recordId2)."""
+    import pandas as pd
+
+    uniq_ids, a, b, count, S = pairwise_link_counts(table, device=device)
+    keep = count >= max(1, min_link_count(min_probability, S))
+    a, b, count = a[keep], b[keep], count[keep]
+    return pd.DataFrame({
+        "recordId1": uniq_ids[a],
+        "recordId2": uniq_ids[b],
+        "probability": count / float(S) if S else count.astype(np.float64),
+    })
+
+
+def save_pairwise_link_probabilities(df, output_path):
+    """CSV ``recordId1,recordId2,probability``; the probability is written
+    with repr(), so it reads back to the same float."""
+    import csv
+
+    path = os.path.join(output_path, PAIR_PROB_FILE)
+    with open(path, "w", encoding="utf-8", newline="") as f:
+        w = csv.writer(f, lineterminator="\n")
+        w.writerow(["recordId1", "recordId2", "probability"])
+        w.writerows(zip(df["recordId1"].tolist(), df["recordId2"].tolist(),
+                        (repr(float(p)) for p in df["probability"].tolist())))
+    return path
+
+
+def read_pairwise_link_probabilities(path):
+    import csv
+
+    import pandas as pd
+
+    if os.path.isdir(path):
+        path = os.path.join(path, PAIR_PROB_FILE)
+    id1, id2, prob = [], [], []
+    with open(path, "r", encoding="utf-8", newline="") as f:
+        rows = csv.reader(f)
+        header = next(rows)
+        if header != ["recordId1", "recordId2", "probability"]:
+            raise ValueError(f"{path}: unexpected header {header}")
+        for r in rows:
+            id1.append(r[0])
+            id2.append(r[1])
+            prob.append(float(r[2]))
+    return pd.DataFrame({
+        "recordId1": np.array(id1, dtype=object),
+        "recordId2": np.array(id2, dtype=object),
+        "probability": np.array(prob, dtype=np.float64),
+    })

@@ -140,3 +140,85 @@ class ClusteringMetrics:
             f" Adj. Rand index: {self.adj_rand_index}\n"
             "=====================================\n"
         )
+
+
+# ---- precision / recall along the link-probability threshold ----------------
+
+CURVE_STEPS = 20  # thresholds k / 20, k = 1..19
+CURVE_FILE = "pairwise-link-curve.csv"
+CURVE_HEADER = ["threshold", "predictedLinks", "trueLinks", "precision", "recall", "f1"]
+
+
+def pairwise_link_curve(uniq_ids, a, b, count, S, true_clusters):
+    """Pairwise precision / recall / F1 of "link every pair whose posterior
+    probability is >= t" for t = 0.05, 0.10, ..., 0.95.
+
+    ``(uniq_ids, a, b, count, S)`` is ``chain.pairwise_link_counts`` output.
+    Works on the integer rank codes: the truth label of each code, one
+    comparison per pair, and ``count * 20 >= k * S`` for the threshold
+    k / 20. Recall is against ALL ground-truth pairs, the sum of s (s - 1) / 2
+    over the true clusters. A ratio with a zero denominator is NaN, as in
+    ``precision`` / ``recall`` / ``f_measure`` above (so precision is NaN
+    where nothing is predicted). Returns one dict per threshold.
+    """
+    import numpy as np
+
+    label_of = {}
+    total_true = 0
+    for lab, cluster in enumerate(true_clusters):
+        total_true += _comb2(len(cluster))
+        for rid in cluster:
+            label_of[rid] = lab
+    labels = np.fromiter((label_of.get(rid, -1) for rid in uniq_ids),
+                         dtype=np.int64, count=len(uniq_ids))
+    a = np.asarray(a, dtype=np.int64)
+    b = np.asarray(b, dtype=np.int64)
+    count = np.asarray(count, dtype=np.int64)
+    is_true = (labels[a] == labels[b]) & (labels[a] >= 0)
+    rows = []
+    for k in range(1, CURVE_STEPS):
+        predicted = count * CURVE_STEPS >= k * int(S)
+        pp = int(predicted.sum())
+        tp = int((predicted & is_true).sum())
+        cm = BinaryConfusionMatrix(tp, pp - tp, total_true - tp)
+        rows.append({
+            "threshold": k / CURVE_STEPS,
+            "predictedLinks": pp,
+            "trueLinks": tp,
+            "precision": precision(cm),
+            "recall": recall(cm),
+            "f1": f_measure(cm, 1.0),
+        })
+    return rows
+
+
+def best_f1_row(rows):
+    """The curve row with the highest F1 (lowest threshold on ties), or
+    None when no threshold has a defined F1."""
+    best = None
+    for r in rows:
+        if r["f1"] == r["f1"] and (best is None or r["f1"] > best["f1"]):
+            best = r
+    return best
+
+
+def save_pairwise_link_curve(rows, output_path):
+    import os
+
+    path = os.path.join(output_path, CURVE_FILE)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(",".join(CURVE_HEADER) + "\n")
+        for r in rows:
+            f.write(",".join(
+                repr(r[h]) if isinstance(r[h], float) else str(r[h])
+                for h in CURVE_HEADER) + "\n")
+    return path
+
+
+def curve_summary_line(rows):
+    best = best_f1_row(rows)
+    if best is None:
+        return "Pairwise link curve: no threshold has a defined F1-score"
+    return (f"Pairwise link curve: best F1-score {best['f1']} at threshold "
+            f"{best['threshold']} (precision {best['precision']}, "
+            f"recall {best['recall']})")

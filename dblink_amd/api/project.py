@@ -34,8 +34,9 @@ from ..utils import hocon
 log = logging.getLogger("dblink_amd.project")
 
 SUPPORTED_SAMPLERS = {"PCG-I", "PCG-II", "Gibbs", "Gibbs-Sequential"}
-SUPPORTED_METRICS = {"pairwise", "cluster"}
-SUPPORTED_QUANTITIES = {"cluster-size-distribution", "partition-sizes", "shared-most-probable-clusters"}
+SUPPORTED_METRICS = {"pairwise", "cluster", "pairwise-curve"}
+SUPPORTED_QUANTITIES = {"cluster-size-distribution", "partition-sizes", "shared-most-probable-clusters",
+                        "pairwise-link-probabilities"}
 
 
 class Project:
@@ -333,6 +334,7 @@ class EvaluateStep:
         true_clusters = self.p.true_clusters()
         smpc_path = os.path.join(self.p.output_path, "shared-most-probable-clusters.csv")
         smpc = None
+        table = None
         if self.use_existing_smpc and os.path.exists(smpc_path):
             smpc = chain_q.read_clusters_csv(smpc_path)
         else:
@@ -353,9 +355,26 @@ class EvaluateStep:
                     results.append(metrics_m.PairwiseMetrics.compute(smpc, true_clusters).mk_string())
                 elif m == "cluster":
                     results.append(metrics_m.ClusteringMetrics.compute(smpc, true_clusters).mk_string())
+            if "pairwise-curve" in self.metrics:
+                # after the sMPC metrics, whose lines stay as they are
+                line = self._link_curve(table, true_clusters)
+                if line is not None:
+                    results.append(line)
             with open(os.path.join(self.p.output_path, "evaluation-results.txt"), "w") as f:
                 f.write("\n".join(results) + "\n")
         comm.barrier()
+
+    def _link_curve(self, table, true_clusters):
+        """Write pairwise-link-curve.csv; returns its one-line summary."""
+        if table is None:  # the sMPC came from its file: the curve needs the chain
+            table = chain_q.load_chain(self.p.output_path, self.cutoff)
+        if table is None:
+            log.error("No linkage chain")
+            return None
+        rows = metrics_m.pairwise_link_curve(
+            *chain_q.pairwise_link_counts(table), true_clusters)
+        metrics_m.save_pairwise_link_curve(rows, self.p.output_path)
+        return metrics_m.curve_summary_line(rows)
 
     def mk_string(self):
         ms = ", ".join(f"'{m}'" for m in self.metrics)
@@ -366,11 +385,15 @@ class EvaluateStep:
 
 
 class SummarizeStep:
-    def __init__(self, project, lower_iteration_cutoff=0, quantities=()):
+    def __init__(self, project, lower_iteration_cutoff=0, quantities=(),
+                 min_link_probability=0.0):
         assert quantities and all(q in SUPPORTED_QUANTITIES for q in quantities)
+        if not 0.0 <= float(min_link_probability) <= 1.0:
+            raise ValueError("`minLinkProbability` must lie in [0, 1].")
         self.p = project
         self.cutoff = lower_iteration_cutoff
         self.quantities = list(quantities)
+        self.min_link_probability = float(min_link_probability)
 
     def execute(self):
         log.info(self.mk_string())
@@ -397,6 +420,12 @@ class SummarizeStep:
                 )
                 chain_q.save_clusters_csv(
                     smpc, os.path.join(self.p.output_path, "shared-most-probable-clusters.csv")
+                )
+            elif q == "pairwise-link-probabilities":
+                chain_q.save_pairwise_link_probabilities(
+                    chain_q.pairwise_link_probabilities(
+                        table, min_probability=self.min_link_probability),
+                    self.p.output_path,
                 )
         comm.barrier()
 
@@ -481,6 +510,7 @@ def parse_steps(config: hocon.Config, project: Project):
                     project,
                     lower_iteration_cutoff=step.get_or("parameters.lowerIterationCutoff", 0),
                     quantities=step.get_string_list("parameters.quantities"),
+                    min_link_probability=step.get_or("parameters.minLinkProbability", 0.0),
                 )
             )
         elif name == "copy-files":

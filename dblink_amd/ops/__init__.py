@@ -61,6 +61,34 @@ def sim_pairs_route(num_values, max_len, num_symbols, cuda_available):
     return "cpu"
 
 
+# Pair occurrences from which the pair-count hash table is taken without
+# being asked for: the smallest measured shape (10^4 records x 100 samples,
+# 4.7M pair occurrences), where the table already beats the numpy arm
+# 116-fold (BENCH.md, "Pairwise link counts"); nothing smaller was measured.
+PAIRS_GPU_MIN_DEFAULT = 1 << 22
+
+
+def have_pair_table() -> bool:
+    return _C is not None and hasattr(_C, "pair_table_add")
+
+
+def pair_counts_route(total_pairs, cuda_available):
+    """Which arm counts the chain's co-clustered pairs: ``"gpu"`` (the
+    pair-count hash table, ``pair_counts.hip``) or ``"numpy"``.
+
+    The GPU arm takes chains of at least ``DBLINK_PAIRS_GPU_MIN`` pair
+    occurrences when a device is available and the extension has the
+    kernels; everything else goes to the numpy reference arm.
+    """
+    min_pairs = int(os.environ.get("DBLINK_PAIRS_GPU_MIN", str(PAIRS_GPU_MIN_DEFAULT)))
+    if cuda_available and have_pair_table() and total_pairs >= min_pairs:
+        return "gpu"
+    return "numpy"
+
+
+from .pair_table import PairCountTable  # noqa: E402,F401
+
+
 def sim_pairs(values, similarity_fn):
     """Build the sparse exp-similarity index over a domain of strings.
 

@@ -253,6 +253,15 @@ std::vector<torch::Tensor> jaro_pairs_gpu(torch::Tensor strs, torch::Tensor lens
                                           double threshold, double max_sim,
                                           double prefix_scale);
 
+// pair_counts.hip
+void pair_table_add(torch::Tensor codes, torch::Tensor cluster_offsets,
+                    torch::Tensor pair_ptr, torch::Tensor keys,
+                    torch::Tensor counts, torch::Tensor occupied,
+                    torch::Tensor err, int64_t total_pairs);
+void pair_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
+                       torch::Tensor new_keys, torch::Tensor new_counts,
+                       torch::Tensor err);
+
 }  // namespace dblink
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -271,6 +280,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "composite (code | count | inv index) sort keys (MPC core)");
   m.def("first_occurrence", &dblink::first_occurrence,
         "first index of each key value");
+  m.def("pair_table_add", &dblink::pair_table_add,
+        "count the member pairs of a chunk of clusters into the pair-count "
+        "hash table (gfx950)",
+        py::arg("codes"), py::arg("cluster_offsets"), py::arg("pair_ptr"),
+        py::arg("keys"), py::arg("counts"), py::arg("occupied"), py::arg("err"),
+        py::arg("total_pairs") = -1);
+  m.def("pair_table_rehash", &dblink::pair_table_rehash,
+        "re-insert a pair-count table's slots into a larger one (gfx950)");
   m.def("distortion_update_cpu", &dblink::distortion_update_cpu,
         "distortion resample (OpenMP, bitwise-matches the numpy fast path)");
   m.def("summary_cpu", &dblink::summary_cpu,

@@ -1,0 +1,254 @@
+// Pair-count hash table (gfx950): co-clustering counts of record pairs over
+// the linkage chain, for the posterior pairwise link probabilities. An
+// extension; the reference has no counterpart.
+//
+// Table: open addressing, linear probing, power-of-two capacity. keys holds
+// (uint64(a) << 32) | b with rank codes a < b < 2^31, so the all-ones EMPTY
+// marker is unreachable; counts is int32. The host grows the table BEFORE an
+// add so that the load factor stays <= 0.5: an insert always finds a slot
+// and a chunk is never half-applied. Every probe loop is bounded by the
+// capacity; a thread that runs out of slots raises the error flag and goes
+// on. No loop here waits on another thread's progress.
+
+#include <ATen/cuda/CUDAContext.h>
+#include <hip/hip_runtime.h>
+#include <torch/extension.h>
+
+#include "common.h"
+
+namespace dblink {
+
+namespace {
+
+constexpr unsigned long long PT_EMPTY = ~0ull;
+constexpr int PT_THREADS = 256;
+constexpr int PT_ITEMS = 8;  // consecutive pair indices per thread
+constexpr int64_t PT_TILE = (int64_t)PT_THREADS * PT_ITEMS;
+constexpr int PT_ERR_FULL = 1;    // probed every slot without success
+constexpr int PT_ERR_BOUNDS = 2;  // pair_ptr and cluster_offsets disagree
+
+DBL_D unsigned long long pt_mix(unsigned long long x) {  // splitmix64 finaliser
+  x += 0x9E3779B97F4A7C15ull;
+  x ^= x >> 30;
+  x *= 0xBF58476D1CE4E5B9ull;
+  x ^= x >> 27;
+  x *= 0x94D049BB133111EBull;
+  x ^= x >> 31;
+  return x;
+}
+
+// Adds `add` to the count of `key`, claiming a slot on first sight. Returns
+// 1 when this thread claimed the slot, 0 on a match, -1 when all `cap` slots
+// were probed in vain. The plain load ahead of the CAS is a shortcut only: a
+// key never changes once written, a stale EMPTY just leads to the CAS, and
+// the CAS returns the truth.
+DBL_D int pt_insert(unsigned long long* __restrict__ keys, int32_t* __restrict__ counts,
+                    unsigned long long cap, unsigned long long key, int32_t add) {
+  const unsigned long long mask = cap - 1;
+  unsigned long long slot = pt_mix(key) & mask;
+  for (unsigned long long n = 0; n < cap; ++n, slot = (slot + 1) & mask) {
+    unsigned long long cur = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
+    int claimed = 0;
+    if (cur == PT_EMPTY) {
+      cur = atomicCAS(&keys[slot], PT_EMPTY, key);
+      if (cur == PT_EMPTY) {
+        cur = key;
+        claimed = 1;
+      }
+    }
+    if (cur == key) {
+      atomicAdd(&counts[slot], add);
+      return claimed;
+    }
+  }
+  return -1;
+}
+
+// First index i in [lo, hi) with arr[i] > key.
+DBL_D int64_t pt_upper_bound(const int64_t* __restrict__ arr, int64_t lo, int64_t hi,
+                             int64_t key) {
+  while (lo < hi) {
+    int64_t mid = (lo + hi) >> 1;
+    if (arr[mid] <= key) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+DBL_D int64_t pt_row_start(int64_t j) { return j * (j - 1) / 2; }
+
+// Cluster-local pair index t -> (i, j), i < j, with t = j (j - 1) / 2 + i.
+// The fp64 root is a first guess only; the integer fix-up makes it exact
+// for every t (an fp32 root is off from t > 2^24).
+DBL_D void pt_decode(int64_t t, int64_t* i, int64_t* j) {
+  int64_t r = (int64_t)((1.0 + sqrt(1.0 + 8.0 * (double)t)) * 0.5);
+  if (r < 1) r = 1;
+  while (pt_row_start(r) > t) --r;
+  while (pt_row_start(r + 1) <= t) ++r;
+  *j = r;
+  *i = t - pt_row_start(r);
+}
+
+// Work is split by GLOBAL PAIR INDEX: a block takes tiles of PT_TILE
+// consecutive pair indices (grid-stride), a thread PT_ITEMS consecutive
+// ones. The tile's cluster range comes from one binary search per tile edge
+// in pair_ptr; a thread searches only that range, then walks forward.
+__global__ void __launch_bounds__(PT_THREADS)
+pair_table_add_kernel(const int32_t* __restrict__ codes, int64_t n_codes,
+                      const int64_t* __restrict__ offsets,
+                      const int64_t* __restrict__ pair_ptr, int64_t C,
+                      int64_t total, unsigned long long* __restrict__ keys,
+                      int32_t* __restrict__ counts, unsigned long long cap,
+                      unsigned long long* __restrict__ occupied,
+                      int32_t* __restrict__ err) {
+  __shared__ int64_t edge[2];
+  const int64_t n_tiles = (total + PT_TILE - 1) / PT_TILE;
+  unsigned int claimed = 0;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    const int64_t t0 = tile * PT_TILE;
+    const int64_t t1 = t0 + PT_TILE < total ? t0 + PT_TILE : total;
+    __syncthreads();  // the previous tile's readers are done with edge[]
+    if (threadIdx.x < 2) {
+      const int64_t p = threadIdx.x == 0 ? t0 : t1 - 1;
+      const int64_t e = pt_upper_bound(pair_ptr, 0, C + 1, p) - 1;
+      edge[threadIdx.x] = e < 0 ? 0 : (e < C ? e : C - 1);
+    }
+    __syncthreads();
+    int64_t p = t0 + (int64_t)threadIdx.x * PT_ITEMS;
+    const int64_t p_end = p + PT_ITEMS < t1 ? p + PT_ITEMS : t1;
+    if (p >= p_end) continue;
+    // the cluster c with pair_ptr[c] <= p < pair_ptr[c + 1]; clusters
+    // without pairs have an empty range and are never landed on
+    int64_t c = pt_upper_bound(pair_ptr, edge[0], edge[1] + 1, p) - 1;
+    if (c < edge[0]) c = edge[0];
+    int64_t c_lo = pair_ptr[c], c_hi = pair_ptr[c + 1], base = offsets[c];
+    for (; p < p_end; ++p) {
+      while (p >= c_hi && c + 1 < C) {
+        ++c;
+        c_lo = c_hi;
+        c_hi = pair_ptr[c + 1];
+        base = offsets[c];
+      }
+      if (p < c_lo || p >= c_hi) {  // pair_ptr does not cover p
+        atomicOr(err, PT_ERR_BOUNDS);
+        continue;
+      }
+      int64_t i, j;
+      pt_decode(p - c_lo, &i, &j);
+      if (base < 0 || base + j >= n_codes) {
+        atomicOr(err, PT_ERR_BOUNDS);
+        continue;
+      }
+      const uint32_t x = (uint32_t)codes[base + i], y = (uint32_t)codes[base + j];
+      if (x == y) continue;  // a duplicated member is no pair
+      const unsigned long long key =
+          ((unsigned long long)(x < y ? x : y) << 32) | (unsigned long long)(x < y ? y : x);
+      const int r = pt_insert(keys, counts, cap, key, 1);
+      if (r < 0) atomicOr(err, PT_ERR_FULL); else claimed += (unsigned)r;
+    }
+  }
+  // one counter update per wave (every lane gets here: the tile loop's
+  // bounds are uniform over the block)
+#pragma unroll
+  for (int off = WAVE / 2; off > 0; off >>= 1) claimed += __shfl_down(claimed, off);
+  if ((threadIdx.x & (WAVE - 1)) == 0 && claimed)
+    atomicAdd(occupied, (unsigned long long)claimed);
+}
+
+__global__ void __launch_bounds__(PT_THREADS)
+pair_table_rehash_kernel(const unsigned long long* __restrict__ old_keys,
+                         const int32_t* __restrict__ old_counts, int64_t old_cap,
+                         unsigned long long* __restrict__ keys,
+                         int32_t* __restrict__ counts, unsigned long long cap,
+                         int32_t* __restrict__ err) {
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < old_cap;
+       s += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = old_keys[s];
+    if (key == PT_EMPTY) continue;
+    if (pt_insert(keys, counts, cap, key, old_counts[s]) < 0)
+      atomicOr(err, PT_ERR_FULL);
+  }
+}
+
+void check_table(const torch::Tensor& keys, const torch::Tensor& counts,
+                 const char* what) {
+  TORCH_CHECK(keys.is_cuda() && counts.is_cuda(), what, ": table must be on the GPU");
+  TORCH_CHECK(keys.is_contiguous() && counts.is_contiguous(), what,
+              ": table must be contiguous");
+  TORCH_CHECK(keys.scalar_type() == torch::kInt64 &&
+              counts.scalar_type() == torch::kInt32, what,
+              ": keys int64, counts int32");
+  const int64_t cap = keys.numel();
+  TORCH_CHECK(cap >= 2 && (cap & (cap - 1)) == 0, what,
+              ": capacity must be a power of two");
+  TORCH_CHECK(counts.numel() == cap, what, ": counts must match keys");
+}
+
+unsigned grid_for(int64_t work_items) {
+  const int64_t cus = at::cuda::getCurrentDeviceProperties()->multiProcessorCount;
+  return (unsigned)std::max<int64_t>(1, std::min<int64_t>(work_items, cus * 8));
+}
+
+}  // namespace
+
+// Counts every member pair of the chunk's clusters into the table.
+// cluster_offsets [C + 1] delimits the clusters in codes; pair_ptr [C + 1]
+// is the exclusive int64 scan of s (s - 1) / 2 with the total last.
+// total_pairs < 0 reads that total back from the device.
+void pair_table_add(torch::Tensor codes, torch::Tensor cluster_offsets,
+                    torch::Tensor pair_ptr, torch::Tensor keys,
+                    torch::Tensor counts, torch::Tensor occupied,
+                    torch::Tensor err, int64_t total_pairs) {
+  check_table(keys, counts, "pair_table_add");
+  TORCH_CHECK(codes.is_cuda() && cluster_offsets.is_cuda() && pair_ptr.is_cuda() &&
+              occupied.is_cuda() && err.is_cuda(),
+              "pair_table_add: all tensors must be on the GPU");
+  TORCH_CHECK(codes.is_contiguous() && cluster_offsets.is_contiguous() &&
+              pair_ptr.is_contiguous(), "pair_table_add: inputs must be contiguous");
+  TORCH_CHECK(codes.scalar_type() == torch::kInt32 &&
+              cluster_offsets.scalar_type() == torch::kInt64 &&
+              pair_ptr.scalar_type() == torch::kInt64,
+              "pair_table_add: codes int32, cluster_offsets and pair_ptr int64");
+  TORCH_CHECK(occupied.scalar_type() == torch::kInt64 && occupied.numel() == 1 &&
+              err.scalar_type() == torch::kInt32 && err.numel() == 1,
+              "pair_table_add: occupied int64 [1], err int32 [1]");
+  const int64_t C = cluster_offsets.numel() - 1;
+  TORCH_CHECK(C >= 0 && pair_ptr.numel() == C + 1,
+              "pair_table_add: pair_ptr must hold one entry per offset");
+  if (C == 0) return;
+  const int64_t total =
+      total_pairs >= 0 ? total_pairs : pair_ptr[C].item<int64_t>();
+  if (total == 0) return;
+  const int64_t n_tiles = (total + PT_TILE - 1) / PT_TILE;
+  hipLaunchKernelGGL(
+      pair_table_add_kernel, dim3(grid_for(n_tiles)), dim3(PT_THREADS), 0,
+      at::cuda::getCurrentCUDAStream(), codes.data_ptr<int32_t>(), codes.numel(),
+      cluster_offsets.data_ptr<int64_t>(), pair_ptr.data_ptr<int64_t>(), C, total,
+      reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>()),
+      counts.data_ptr<int32_t>(), (unsigned long long)keys.numel(),
+      reinterpret_cast<unsigned long long*>(occupied.data_ptr<int64_t>()),
+      err.data_ptr<int32_t>());
+}
+
+// Re-inserts every occupied slot of the old table, with its count, into the
+// new (EMPTY-filled, zero-count) one.
+void pair_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
+                       torch::Tensor new_keys, torch::Tensor new_counts,
+                       torch::Tensor err) {
+  check_table(old_keys, old_counts, "pair_table_rehash (old)");
+  check_table(new_keys, new_counts, "pair_table_rehash (new)");
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == torch::kInt32 &&
+              err.numel() == 1, "pair_table_rehash: err int32 [1] on the GPU");
+  TORCH_CHECK(new_keys.data_ptr() != old_keys.data_ptr(),
+              "pair_table_rehash: tables must differ");
+  const int64_t old_cap = old_keys.numel();
+  hipLaunchKernelGGL(
+      pair_table_rehash_kernel, dim3(grid_for((old_cap + PT_THREADS - 1) / PT_THREADS)),
+      dim3(PT_THREADS), 0, at::cuda::getCurrentCUDAStream(),
+      reinterpret_cast<const unsigned long long*>(old_keys.data_ptr<int64_t>()),
+      old_counts.data_ptr<int32_t>(), old_cap,
+      reinterpret_cast<unsigned long long*>(new_keys.data_ptr<int64_t>()),
+      new_counts.data_ptr<int32_t>(), (unsigned long long)new_keys.numel(),
+      err.data_ptr<int32_t>());
+}
+
+}  // namespace dblink

@@ -25,6 +25,7 @@ ext = CUDAExtension(
         os.path.join(CSRC, "sim_pairs_cpu.cpp"),
         os.path.join(CSRC, "link_dense_cpu.cpp"),
         os.path.join(CSRC, "kernels.hip"),
+        os.path.join(CSRC, "pair_counts.hip"),
     ],
     include_dirs=[CSRC],
     extra_compile_args={
