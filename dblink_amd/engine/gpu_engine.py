@@ -378,9 +378,21 @@ class GpuEngine(CpuEngine):
         # stand-alone cand_ranges launch (default: the scan clears the
         # counters, the scatter launch computes the ranges);
         # DBLINK_VALUE_MERGE=0 keeps one launch per thread-per-pair value
-        # class (default: value_update_thread_kernel covers all three)
+        # class (default: value_update_thread_kernel covers all three);
+        # DBLINK_TAIL_MERGE=0 keeps partition_resort and summary_counts as
+        # two ops, six launches (default: sweep_tail, three launches).
+        # (DBLINK_RESORT_SCAN=0, read by the native re-sort itself, keeps
+        # the scan of the re-sort's tile histograms a launch of its own.)
         self._index_merge = os.environ.get("DBLINK_INDEX_MERGE", "1") != "0"
         self._value_merge = os.environ.get("DBLINK_VALUE_MERGE", "1") != "0"
+        self._tail_merge = os.environ.get("DBLINK_TAIL_MERGE", "1") != "0"
+        # DBLINK_BEGIN_MERGE=0 keeps the staging copy, the counter fill and
+        # the posting histogram three launches (default: sweep_begin);
+        # DBLINK_LINK_MERGE=0 keeps the wave kernel building the split list
+        # and the split kernel a launch of its own (default: the list is
+        # built with the candidate ranges, link_update_merged serves both)
+        self._begin_merge = os.environ.get("DBLINK_BEGIN_MERGE", "1") != "0"
+        self._link_merge = os.environ.get("DBLINK_LINK_MERGE", "1") != "0"
         # True while _idx_counts is known to be all zero (left so by the
         # clearing scan), so the next histogram needs no fill
         self._idx_clean = False
@@ -512,13 +524,15 @@ class GpuEngine(CpuEngine):
             self._idx_counts.zero_()
         return nk
 
-    def _zero_counters(self, E):
+    def _zero_counters(self, E, fill=True):
         """One fill for everything the fused sweep accumulates into: the
         log-likelihood partials, the summary counts, the link split list's
         counter, the value pair-list counters, the per-entity record counts and kobs live in one block
-        (typed views of it)."""
+        (typed views of it). With ``fill`` off the caller zeroes the block
+        itself (sweep_begin)."""
         if self._zero_E == E:
-            self._zero_blk.zero_()
+            if fill:
+                self._zero_blk.zero_()
             return
         A = self.model.A
         n_ll, n_c = 2 * self._loglik_buf.numel(), 2 * self._counts.numel()
@@ -745,7 +759,6 @@ class GpuEngine(CpuEngine):
         dev = self.device
 
         self._mark("start", graph_safe)
-        self._stage.copy_(self._stage_pin, non_blocking=True)  # ctrl + theta
         ctrl = self._ctrl
         seed, it = 0, 0  # kernels read the ctrl buffer
         # posting histogram possibly pre-built during the previous sweep's
@@ -756,8 +769,17 @@ class GpuEngine(CpuEngine):
 
         fused = self._fused
         resort_fused = self._resort_fused_ok()
+        dense_idx = (not flags.sequential and not flags.collapsed_entity_ids
+                     and self.num_partitions * (A + self._num_pairs)
+                     * max(m.Vmax, self._pair_vmax) <= (1 << 28))
+        # single-rank sweep head: the histogram's launch also copies ctrl +
+        # theta off the pinned staging words and zeroes the counter block
+        begin_merge = (fused and self._begin_merge and self.world_size <= 1
+                       and dense_idx and not hist_pre)
+        if not begin_merge:
+            self._stage.copy_(self._stage_pin, non_blocking=True)  # ctrl + theta
         if fused:
-            self._zero_counters(E)
+            self._zero_counters(E, fill=not begin_merge)
             glue = self._glue_bufs(E, R)
 
         if resort_fused and self._ent_ptr_valid:
@@ -773,20 +795,26 @@ class GpuEngine(CpuEngine):
         # enumerate ranges (membership checks are entity-value compares) and
         # Gumbel draws are keyed by entity id, so no stable sort is needed.
         # Ranges come straight off the dense key prefix — no searchsorted.
-        dense_idx = False
+        link_merge = False
         if not flags.sequential and not flags.collapsed_entity_ids:
             T = A + self._num_pairs
             vmax = max(m.Vmax, self._pair_vmax)
             nk = self.num_partitions * T * vmax
-            if nk <= (1 << 28):  # dense counters (1 GiB cap; always true in practice)
-                dense_idx = True
+            if dense_idx:  # dense counters (1 GiB cap; always true in practice)
                 if not hist_pre:
                     # no fill while the previous sweep's scan left them zero
                     self._ensure_idx_buffers(zero=not self._idx_clean)
                     self._idx_clean = False
-                    self.C.postings_hist(gs.ent_part, gs.ent_values, self._pair_a1,
-                                         self._pair_a2, self._pair_v2, vmax,
-                                         self._idx_counts)
+                    if begin_merge:
+                        self.C.sweep_begin(gs.ent_part, gs.ent_values,
+                                           self._pair_a1, self._pair_a2,
+                                           self._pair_v2, vmax, self._idx_counts,
+                                           self._zero_blk, self._stage_pin,
+                                           self._stage)
+                    else:
+                        self.C.postings_hist(gs.ent_part, gs.ent_values,
+                                             self._pair_a1, self._pair_a2,
+                                             self._pair_v2, vmax, self._idx_counts)
                 heavy_sort = self._heavy_active(R) or \
                     os.environ.get("DBLINK_FORCE_SORT", "") == "1"
                 index_merge = fused and self._index_merge
@@ -825,7 +853,22 @@ class GpuEngine(CpuEngine):
                     postings = torch.empty(T * E, dtype=torch.int32, device=dev)
                 cand_lo = torch.empty((R, T), dtype=torch.int64, device=dev)
                 cand_hi = torch.empty((R, T), dtype=torch.int64, device=dev)
-                if index_merge and not heavy_sort:
+                split_len = self._split_len if R < self._split_max_records else 0
+                # the split decision needs only what this launch reads, so the
+                # list is built here and the link phase is one launch
+                link_merge = (index_merge and not heavy_sort and self._link_merge
+                              and self.world_size <= 1 and split_len > 0
+                              and R < 50_000)
+                if link_merge:
+                    if self._split_list.numel() != R:
+                        self._split_list = torch.empty(R, dtype=torch.int32, device=dev)
+                    self.C.postings_scatter_ranges_split(
+                        gs.ent_part, gs.ent_values, gs.rec_part, gs.rec_values,
+                        self._pair_a1, self._pair_a2, self._pair_v2, vmax,
+                        self._idx_cursor, self._idx_ptr, postings, cand_lo, cand_hi,
+                        gs.rec_dist, m.attr_const, ent_ptr, self._split_list,
+                        self._split_cnt, split_len)
+                elif index_merge and not heavy_sort:
                     # scatter and ranges both hang off the scan: one launch
                     self.C.postings_scatter_ranges(
                         gs.ent_part, gs.ent_values, gs.rec_part, gs.rec_values,
@@ -861,6 +904,17 @@ class GpuEngine(CpuEngine):
                 gs.ent_values, ent_ptr, m.theta, m.phi, m.norm_lin, m.voff,
                 m.csr_row_ptr, m.csr_col, m.csr_sim, m.attr_const,
                 1 if flags.collapsed_entity_ids else 0, seed, it, rec_ent_new, ctrl,
+            )
+        elif link_merge:
+            # every record on the wave or the split path (no mode routing
+            # below 50,000 records), the list already built: one launch
+            self.C.link_update_merged(
+                gs.rec_values, gs.rec_dist, gs.rec_gid, gs.rec_part,
+                cand_lo, cand_hi, postings, gs.ent_values,
+                ent_ptr, m.log_norm, m.voff, m.csr_row_ptr, m.csr_col, m.csr_sim,
+                m.attr_const, seed, it, rec_ent_new, gs.rec_ent, self._err, ctrl,
+                self._pair_a1, self._pair_a2, self._split_list, self._split_cnt,
+                split_len, self._split_grid,
             )
         else:
             # three-way routing, all device-side (no host sync, graph-safe):
@@ -986,6 +1040,21 @@ class GpuEngine(CpuEngine):
         summary. isolate COUNT is permutation-invariant, so the pre-sort CSR
         is still valid for the summary counts."""
         if self.world_size > 1:
+            return
+        if resort_fused and self._tail_merge:
+            # re-sort and summary as one op: three launches for six
+            t, glue = self.flat_tree, self._glue_bufs(gs.E, gs.R)
+            self.C.sweep_tail(
+                gs.ent_values, gs.ent_part, gs.rec_ent, t["kind"], t["attr"],
+                t["a"], t["b"], t["rset"], self.num_partitions, glue["hist"],
+                glue["tile_base"], glue["inv"], gs_out.ent_part,
+                gs_out.ent_values, gs_out.rec_ent, gs_out.rec_part, self._ent_ptr,
+                gs_out.rec_dist, gs_out.rec_file, ent_rec_ptr, self._counts,
+                self._loglik_buf, self._packed, self._err,
+            )
+            self._ent_ptr_valid = True
+            self._mark("sort", graph_safe)
+            self._mark("summary", graph_safe)
             return
         if resort_fused:
             self._resort_into(gs, gs_out)

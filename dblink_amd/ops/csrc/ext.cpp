@@ -243,6 +243,39 @@ void partition_resort(torch::Tensor ent_values, torch::Tensor ent_part,
                       torch::Tensor inv, torch::Tensor out_ent_part,
                       torch::Tensor out_ent_values, torch::Tensor out_rec_ent,
                       torch::Tensor out_rec_part, torch::Tensor ent_ptr);
+void sweep_begin(torch::Tensor ent_part, torch::Tensor ent_values,
+                 torch::Tensor pair_a1, torch::Tensor pair_a2,
+                 torch::Tensor pair_v2, int64_t Vmax, torch::Tensor counts,
+                 torch::Tensor zero_blk, torch::Tensor stage_pin,
+                 torch::Tensor stage);
+void postings_scatter_ranges_split(
+    torch::Tensor ent_part, torch::Tensor ent_values, torch::Tensor rec_part,
+    torch::Tensor rec_values, torch::Tensor pair_a1, torch::Tensor pair_a2,
+    torch::Tensor pair_v2, int64_t Vmax, torch::Tensor cursor, torch::Tensor ptr,
+    torch::Tensor postings, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor rec_dist, torch::Tensor attr_const, torch::Tensor ent_ptr,
+    torch::Tensor split_list, torch::Tensor split_count, int64_t split_len);
+void link_update_merged(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
+    torch::Tensor rec_part, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor postings, torch::Tensor ent_values, torch::Tensor ent_ptr,
+    torch::Tensor log_norm, torch::Tensor voff, torch::Tensor csr_row_ptr,
+    torch::Tensor csr_col, torch::Tensor csr_sim, torch::Tensor attr_const,
+    int64_t seed, int64_t iteration, torch::Tensor rec_ent_out,
+    torch::Tensor rec_ent_in, torch::Tensor error_count, torch::Tensor ctrl,
+    torch::Tensor pair_a1, torch::Tensor pair_a2, torch::Tensor split_list,
+    torch::Tensor split_count, int64_t split_len, int64_t split_grid);
+void sweep_tail(torch::Tensor ent_values, torch::Tensor ent_part,
+                torch::Tensor rec_ent, torch::Tensor node_kind,
+                torch::Tensor node_attr, torch::Tensor node_a,
+                torch::Tensor node_b, torch::Tensor rset, int64_t P,
+                torch::Tensor hist, torch::Tensor tile_base, torch::Tensor inv,
+                torch::Tensor out_ent_part, torch::Tensor out_ent_values,
+                torch::Tensor out_rec_ent, torch::Tensor out_rec_part,
+                torch::Tensor ent_ptr, torch::Tensor rec_dist,
+                torch::Tensor rec_file, torch::Tensor ent_rec_ptr,
+                torch::Tensor counts, torch::Tensor loglik, torch::Tensor packed,
+                torch::Tensor err);
 void kd_descent(torch::Tensor ent_values, torch::Tensor node_kind,
                 torch::Tensor node_attr, torch::Tensor node_a, torch::Tensor node_b,
                 torch::Tensor rset, torch::Tensor ent_part_out);
@@ -355,6 +388,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "histogram counters partition_resort needs");
   m.def("partition_resort", &dblink::partition_resort,
         "K9 KD descent + stable partition re-sort + record remap");
+  m.def("sweep_begin", &dblink::sweep_begin,
+        "posting histogram, counter-block fill and staging copy, one launch");
+  m.def("postings_scatter_ranges_split", &dblink::postings_scatter_ranges_split,
+        "postings_scatter_ranges that also builds the link split list");
+  m.def("link_update_merged", &dblink::link_update_merged,
+        "link update, split and wave blocks in one launch");
+  m.def("sweep_tail", &dblink::sweep_tail,
+        "partition_resort + summary_counts in three launches");
   m.def("set_value_stats", &dblink::set_value_stats,
         "install the optional value-phase work-counter buffer");
   m.def("set_value_ktables", &dblink::set_value_ktables,

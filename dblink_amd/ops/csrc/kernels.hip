@@ -170,26 +170,33 @@ struct LinkBase {
 // pseudo slots; a pair base implies both constituents match, but every nd
 // single must still be value-checked (check_mask keeps them all). Without
 // any nd attr the base is the record's whole partition.
-DBL_D LinkBase link_select_base(const int64_t* __restrict__ cand_lo,
-                                const int64_t* __restrict__ cand_hi,
-                                const int32_t* __restrict__ pair_a1,
-                                const int32_t* __restrict__ pair_a2, int NP,
-                                const int32_t* __restrict__ rec_part,
-                                const int64_t* __restrict__ ent_ptr,
-                                int64_t r, int A, uint32_t nd_mask) {
-  const int T = A + NP;
+//
+// range(t) gives slot t's candidate range of record r: the stored cand_lo/hi
+// for the link kernels, the key prefix itself where the ranges are being
+// written in the same launch.
+struct CandRange { int64_t lo, hi; };
+
+template <class Range>
+DBL_D LinkBase link_select_base_from(const Range& range,
+                                     const int32_t* __restrict__ pair_a1,
+                                     const int32_t* __restrict__ pair_a2, int NP,
+                                     const int32_t* __restrict__ rec_part,
+                                     const int64_t* __restrict__ ent_ptr,
+                                     int64_t r, int A, uint32_t nd_mask) {
   int base_attr = -1;
   LinkBase b{0, INT64_MAX, 0, true};
   for (uint32_t m = nd_mask; m;) {
     const int a = __ffs(m) - 1;
     m &= m - 1;
-    const int64_t lo = cand_lo[r * T + a], n = cand_hi[r * T + a] - lo;
+    const CandRange c = range(a);
+    const int64_t lo = c.lo, n = c.hi - lo;
     if (n < b.n) { b.n = n; b.lo = lo; base_attr = a; }
   }
   for (int t = 0; t < NP; ++t) {
     const int a1 = pair_a1[t], a2 = pair_a2[t];
     if (((nd_mask >> a1) & 1u) == 0 || ((nd_mask >> a2) & 1u) == 0) continue;
-    const int64_t lo = cand_lo[r * T + A + t], n = cand_hi[r * T + A + t] - lo;
+    const CandRange c = range(A + t);
+    const int64_t lo = c.lo, n = c.hi - lo;
     if (n < b.n) { b.n = n; b.lo = lo; base_attr = -1; }
   }
   if (nd_mask == 0) {
@@ -200,6 +207,19 @@ DBL_D LinkBase link_select_base(const int64_t* __restrict__ cand_lo,
   }
   b.check_mask = base_attr >= 0 ? (nd_mask & ~(1u << base_attr)) : nd_mask;
   return b;
+}
+
+DBL_D LinkBase link_select_base(const int64_t* __restrict__ cand_lo,
+                                const int64_t* __restrict__ cand_hi,
+                                const int32_t* __restrict__ pair_a1,
+                                const int32_t* __restrict__ pair_a2, int NP,
+                                const int32_t* __restrict__ rec_part,
+                                const int64_t* __restrict__ ent_ptr,
+                                int64_t r, int A, uint32_t nd_mask) {
+  const int T = A + NP;
+  return link_select_base_from(
+      [&](int t) { return CandRange{cand_lo[r * T + t], cand_hi[r * T + t]}; },
+      pair_a1, pair_a2, NP, rec_part, ent_ptr, r, A, nd_mask);
 }
 
 // Entity e equals record r on every attribute in mask.
@@ -258,7 +278,9 @@ DBL_D long long link_winner_or_keep(long long best_e,
 // is what lets the index build be an unstable counting sort.
 // ---------------------------------------------------------------------------
 
-__global__ void link_update_kernel(
+// One wave scans record r's base list (the body of link_update_kernel and of
+// the wave blocks of link_update_merged_kernel).
+DBL_D void link_wave_record(
     const int32_t* __restrict__ rec_values,  // [R, A]
     const uint8_t* __restrict__ rec_dist,    // [R, A]
     const int64_t* __restrict__ rec_gid,     // [R]
@@ -284,12 +306,10 @@ __global__ void link_update_kernel(
     int* __restrict__ error_count, int simh_on,
     int64_t split_len,                       // 0 = no split path
     int32_t* __restrict__ split_list,        // [R] records left to the split kernel
-    int* __restrict__ split_count) {
+    int* __restrict__ split_count,           // null: the list was built earlier
+    int32_t* simh_k, float* simh_v,          // this wave's SIMH_CAP-entry LDS tables
+    int64_t r) {
   const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  __shared__ int32_t simh_k_s[4][SIMH_CAP];  // launcher uses WPB == 4
-  __shared__ float simh_v_s[4][SIMH_CAP];
-  int64_t r = (int64_t)blockIdx.x * (blockDim.x / WAVE) + wid;
   if (r >= R) return;
   if (small_mask != nullptr && small_mask[r]) return;
   ctrl_override(ctrl, seed, iteration);
@@ -303,7 +323,8 @@ __global__ void link_update_kernel(
   // a list longer than split_len is not scanned by one wave: the record goes
   // on the list that link_update_split_kernel serves in the next launch
   if (split_len > 0 && base.n > split_len) {
-    if (lane == 0) split_list[atomicAdd(split_count, 1)] = (int32_t)r;
+    if (lane == 0 && split_count != nullptr)
+      split_list[atomicAdd(split_count, 1)] = (int32_t)r;
     return;
   }
 
@@ -311,8 +332,6 @@ __global__ void link_update_kernel(
   // stage this record's od-attr sim rows into LDS when the scan is long
   // enough to amortize the fill (short scans: the binary search is cheaper)
   uint64_t logpk = 0, offpk = 0;
-  int32_t* simh_k = simh_k_s[wid];
-  float* simh_v = simh_v_s[wid];
   if (simh_on && od_mask && base.n * __popc(od_mask) >= 32)
     simh_stage<WAVE>(simh_k, simh_v, lane, csr_row_ptr, csr_col, csr_sim, voff,
                rec_values, r, A, od_mask, logpk, offpk);
@@ -334,6 +353,32 @@ __global__ void link_update_kernel(
   wave_argmax(best_score, best_e);
   if (lane == 0)
     rec_ent_out[r] = link_winner_or_keep(best_e, rec_ent_in, r, error_count);
+}
+
+__global__ void link_update_kernel(
+    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
+    const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
+    const int64_t* __restrict__ cand_lo, const int64_t* __restrict__ cand_hi,
+    const int32_t* __restrict__ postings, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ ent_ptr, const float* __restrict__ log_norm,
+    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
+    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
+    const uint8_t* __restrict__ attr_const, const int32_t* __restrict__ pair_a1,
+    const int32_t* __restrict__ pair_a2, int NP,
+    const uint8_t* __restrict__ small_mask, int64_t R, int A, uint64_t seed,
+    uint32_t iteration, const int64_t* __restrict__ ctrl,
+    int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
+    int* __restrict__ error_count, int simh_on, int64_t split_len,
+    int32_t* __restrict__ split_list, int* __restrict__ split_count) {
+  __shared__ int32_t simh_k_s[4][SIMH_CAP];  // launcher uses WPB == 4
+  __shared__ float simh_v_s[4][SIMH_CAP];
+  const int wid = threadIdx.x / WAVE;
+  link_wave_record(rec_values, rec_dist, rec_gid, rec_part, cand_lo, cand_hi, postings,
+                   ent_values, ent_ptr, log_norm, voff, csr_row_ptr, csr_col, csr_sim,
+                   attr_const, pair_a1, pair_a2, NP, small_mask, R, A, seed, iteration,
+                   ctrl, rec_ent_out, rec_ent_in, error_count, simh_on, split_len,
+                   split_list, split_count, simh_k_s[wid], simh_v_s[wid],
+                   (int64_t)blockIdx.x * (blockDim.x / WAVE) + wid);
 }
 
 // Thread-per-record link update for records whose smallest candidate list is
@@ -408,7 +453,11 @@ DBL_D bool link_split_better(float s_a, int64_t i_a, float s_b, int64_t i_b) {
   return i_a < i_b;
 }
 
-__global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
+// The block serves entries first, first + stride, ... of the list (the body
+// of link_update_split_kernel and of the split blocks of
+// link_update_merged_kernel). simh_k/simh_v: SIMH_CAP entries; red_*: one
+// slot per wave.
+DBL_D void link_split_block(
     const int32_t* __restrict__ split_list, const int* __restrict__ split_count,
     const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
     const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
@@ -421,12 +470,8 @@ __global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
     const int32_t* __restrict__ pair_a2, int NP, int A, uint64_t seed,
     uint32_t iteration, const int64_t* __restrict__ ctrl,
     int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
-    int* __restrict__ error_count, int simh_on) {
-  __shared__ int32_t simh_k[SIMH_CAP];
-  __shared__ float simh_v[SIMH_CAP];
-  __shared__ float red_s[LINK_SPLIT_WAVES];
-  __shared__ int64_t red_i[LINK_SPLIT_WAVES];
-  __shared__ long long red_e[LINK_SPLIT_WAVES];
+    int* __restrict__ error_count, int simh_on, int32_t* simh_k, float* simh_v,
+    float* red_s, int64_t* red_i, long long* red_e, int first, int stride) {
   const int tid = threadIdx.x;
   const int lane = tid & (WAVE - 1);
   const int wid = tid / WAVE;
@@ -434,7 +479,7 @@ __global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
   // the list was completed by the previous launch; a list longer than the
   // (static) grid is served by the stride
   const int n_listed = *split_count;
-  for (int j = blockIdx.x; j < n_listed; j += gridDim.x) {
+  for (int j = first; j < n_listed; j += stride) {
     const int64_t r = split_list[j];
     const auto [nd_mask, od_mask] =
         link_classify(rec_values, rec_dist, attr_const, r, A);
@@ -486,6 +531,80 @@ __global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
     // no barrier here: the next record's staging touches simh_* only, which
     // every wave has finished probing, and red_* is rewritten behind the
     // barrier above, which thread 0 reaches after this combine
+  }
+}
+
+__global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_split_kernel(
+    const int32_t* __restrict__ split_list, const int* __restrict__ split_count,
+    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
+    const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
+    const int64_t* __restrict__ cand_lo, const int64_t* __restrict__ cand_hi,
+    const int32_t* __restrict__ postings, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ ent_ptr, const float* __restrict__ log_norm,
+    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
+    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
+    const uint8_t* __restrict__ attr_const, const int32_t* __restrict__ pair_a1,
+    const int32_t* __restrict__ pair_a2, int NP, int A, uint64_t seed,
+    uint32_t iteration, const int64_t* __restrict__ ctrl,
+    int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
+    int* __restrict__ error_count, int simh_on) {
+  __shared__ int32_t simh_k[SIMH_CAP];
+  __shared__ float simh_v[SIMH_CAP];
+  __shared__ float red_s[LINK_SPLIT_WAVES];
+  __shared__ int64_t red_i[LINK_SPLIT_WAVES];
+  __shared__ long long red_e[LINK_SPLIT_WAVES];
+  link_split_block(split_list, split_count, rec_values, rec_dist, rec_gid, rec_part,
+                   cand_lo, cand_hi, postings, ent_values, ent_ptr, log_norm, voff,
+                   csr_row_ptr, csr_col, csr_sim, attr_const, pair_a1, pair_a2, NP, A,
+                   seed, iteration, ctrl, rec_ent_out, rec_ent_in, error_count, simh_on,
+                   simh_k, simh_v, red_s, red_i, red_e, (int)blockIdx.x,
+                   (int)gridDim.x);
+}
+
+// Link phase in one launch, once the split list exists before it (built with
+// the candidate ranges): blocks [0, n_split) serve the list, the blocks after
+// them are wave blocks of LINK_SPLIT_WAVES records each, which skip a listed
+// record. The two kinds share no data. The per-wave tables fill the 64 KiB of
+// static LDS; a split block uses wave 0's tables and keeps its reduction
+// slots in wave 1's key table.
+__global__ void __launch_bounds__(LINK_SPLIT_THREADS) link_update_merged_kernel(
+    const int32_t* __restrict__ split_list, const int* __restrict__ split_count,
+    const int32_t* __restrict__ rec_values, const uint8_t* __restrict__ rec_dist,
+    const int64_t* __restrict__ rec_gid, const int32_t* __restrict__ rec_part,
+    const int64_t* __restrict__ cand_lo, const int64_t* __restrict__ cand_hi,
+    const int32_t* __restrict__ postings, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ ent_ptr, const float* __restrict__ log_norm,
+    const int64_t* __restrict__ voff, const int64_t* __restrict__ csr_row_ptr,
+    const int32_t* __restrict__ csr_col, const float* __restrict__ csr_sim,
+    const uint8_t* __restrict__ attr_const, const int32_t* __restrict__ pair_a1,
+    const int32_t* __restrict__ pair_a2, int NP, int64_t R, int A, uint64_t seed,
+    uint32_t iteration, const int64_t* __restrict__ ctrl,
+    int64_t* __restrict__ rec_ent_out, const int64_t* __restrict__ rec_ent_in,
+    int* __restrict__ error_count, int simh_on, int64_t split_len, unsigned n_split) {
+  __shared__ __attribute__((aligned(16))) int32_t simh_k_s[LINK_SPLIT_WAVES][SIMH_CAP];
+  __shared__ __attribute__((aligned(16))) float simh_v_s[LINK_SPLIT_WAVES][SIMH_CAP];
+  static_assert(SIMH_CAP * sizeof(int32_t) >=
+                    LINK_SPLIT_WAVES * (sizeof(float) + 2 * sizeof(int64_t)),
+                "reduction slots must fit one wave's key table");
+  if (blockIdx.x < n_split) {
+    int64_t* red_i = reinterpret_cast<int64_t*>(simh_k_s[1]);
+    long long* red_e = reinterpret_cast<long long*>(red_i + LINK_SPLIT_WAVES);
+    float* red_s = reinterpret_cast<float*>(red_e + LINK_SPLIT_WAVES);
+    link_split_block(split_list, split_count, rec_values, rec_dist, rec_gid, rec_part,
+                     cand_lo, cand_hi, postings, ent_values, ent_ptr, log_norm, voff,
+                     csr_row_ptr, csr_col, csr_sim, attr_const, pair_a1, pair_a2, NP,
+                     A, seed, iteration, ctrl, rec_ent_out, rec_ent_in, error_count,
+                     simh_on, simh_k_s[0], simh_v_s[0], red_s, red_i, red_e,
+                     (int)blockIdx.x, (int)n_split);
+  } else {
+    const int wid = threadIdx.x / WAVE;
+    link_wave_record(rec_values, rec_dist, rec_gid, rec_part, cand_lo, cand_hi,
+                     postings, ent_values, ent_ptr, log_norm, voff, csr_row_ptr,
+                     csr_col, csr_sim, attr_const, pair_a1, pair_a2, NP, nullptr, R, A,
+                     seed, iteration, ctrl, rec_ent_out, rec_ent_in, error_count,
+                     simh_on, split_len, nullptr, nullptr, simh_k_s[wid],
+                     simh_v_s[wid],
+                     (int64_t)(blockIdx.x - n_split) * LINK_SPLIT_WAVES + wid);
   }
 }
 
@@ -2197,7 +2316,8 @@ DBL_D int pb_hash(int32_t key) {
   return (int)(((uint32_t)key * 2654435761u) >> 16) & (PB_TBL - 1);
 }
 
-__global__ __launch_bounds__(PB_THREADS) void postings_hist_kernel(
+// Histogram of block blockIdx.x's PB_THREADS (slot, entity) items.
+DBL_D void postings_hist_block(
     const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
     const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
     const int32_t* __restrict__ pair_v2, int64_t E, int A, int NP, int64_t Vmax,
@@ -2229,6 +2349,15 @@ __global__ __launch_bounds__(PB_THREADS) void postings_hist_kernel(
   __syncthreads();
   for (int i = threadIdx.x; i < PB_TBL; i += blockDim.x)
     if (h_key[i] >= 0) atomicAdd(&counts[h_key[i]], h_cnt[i]);
+}
+
+__global__ __launch_bounds__(PB_THREADS) void postings_hist_kernel(
+    const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, int64_t E, int A, int NP, int64_t Vmax,
+    int32_t* __restrict__ counts) {
+  postings_hist_block(ent_part, ent_values, pair_a1, pair_a2, pair_v2, E, A, NP, Vmax,
+                      counts);
 }
 
 // Scatter of block blockIdx.x's PB_THREADS (slot, entity) items.
@@ -2320,7 +2449,27 @@ __global__ void classify_modes_kernel(
   mode[r] = m;
 }
 
-// Candidate range of (record, slot) item idx off the dense key prefix.
+// Candidate range of record r's slot t off the dense key prefix.
+DBL_D CandRange cand_range_of(
+    const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, const int64_t* __restrict__ ptr,
+    int A, int NP, int64_t Vmax, int64_t r, int t) {
+  int64_t v;
+  if (t < A) {
+    v = rec_values[r * A + t];
+  } else {
+    const int32_t x1 = rec_values[r * A + pair_a1[t - A]];
+    const int32_t x2 = rec_values[r * A + pair_a2[t - A]];
+    v = (x1 < 0 || x2 < 0) ? -1 : (int64_t)x1 * pair_v2[t - A] + x2;
+  }
+  // missing value: empty range (never consulted as a constraint)
+  if (v < 0) return {0, 0};
+  const int64_t key = ((int64_t)rec_part[r] * (A + NP) + t) * Vmax + v;
+  return {ptr[key], ptr[key + 1]};
+}
+
+// The same for (record, slot) item idx, stored.
 DBL_D void cand_range_item(
     const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
     const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
@@ -2330,24 +2479,10 @@ DBL_D void cand_range_item(
     int64_t idx) {
   const int T = A + NP;
   if (idx >= R * T) return;
-  const int64_t r = idx / T;
-  const int t = (int)(idx % T);
-  int64_t v;
-  if (t < A) {
-    v = rec_values[r * A + t];
-  } else {
-    const int32_t x1 = rec_values[r * A + pair_a1[t - A]];
-    const int32_t x2 = rec_values[r * A + pair_a2[t - A]];
-    v = (x1 < 0 || x2 < 0) ? -1 : (int64_t)x1 * pair_v2[t - A] + x2;
-  }
-  if (v < 0) {  // missing value: empty range (never consulted as a constraint)
-    cand_lo[idx] = 0;
-    cand_hi[idx] = 0;
-    return;
-  }
-  const int64_t key = ((int64_t)rec_part[r] * T + t) * Vmax + v;
-  cand_lo[idx] = ptr[key];
-  cand_hi[idx] = ptr[key + 1];
+  const CandRange c = cand_range_of(rec_part, rec_values, pair_a1, pair_a2, pair_v2,
+                                    ptr, A, NP, Vmax, idx / T, (int)(idx % T));
+  cand_lo[idx] = c.lo;
+  cand_hi[idx] = c.hi;
 }
 
 __global__ void cand_ranges_kernel(
@@ -2382,20 +2517,60 @@ __global__ __launch_bounds__(PB_THREADS) void postings_scatter_ranges_kernel(
   }
 }
 
+// The same launch with the link phase's split list built in it: a range block
+// takes one thread per record, writes the record's T ranges and appends the
+// record to split_list when its base list (the one the link kernels will
+// select) is longer than split_len. split_count must be zero on entry; the
+// order within the list is arbitrary.
+__global__ __launch_bounds__(PB_THREADS) void postings_scatter_ranges_split_kernel(
+    const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ rec_part, const int32_t* __restrict__ rec_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, const int64_t* __restrict__ ptr,
+    int64_t E, int64_t R, int A, int NP, int64_t Vmax, unsigned n_scatter,
+    int32_t* __restrict__ cursor, int32_t* __restrict__ postings,
+    int64_t* __restrict__ cand_lo, int64_t* __restrict__ cand_hi,
+    const uint8_t* __restrict__ rec_dist, const uint8_t* __restrict__ attr_const,
+    const int64_t* __restrict__ ent_ptr, int64_t split_len,
+    int32_t* __restrict__ split_list, int* __restrict__ split_count) {
+  if (blockIdx.x < n_scatter) {
+    postings_scatter_block(ent_part, ent_values, pair_a1, pair_a2, pair_v2, E, A,
+                           NP, Vmax, cursor, postings);
+    return;
+  }
+  const int64_t r = (int64_t)(blockIdx.x - n_scatter) * PB_THREADS + threadIdx.x;
+  if (r >= R) return;
+  const int T = A + NP;
+  const auto range = [&](int t) {
+    return cand_range_of(rec_part, rec_values, pair_a1, pair_a2, pair_v2, ptr, A, NP,
+                         Vmax, r, t);
+  };
+  for (int t = 0; t < T; ++t) {
+    const CandRange c = range(t);
+    cand_lo[r * T + t] = c.lo;
+    cand_hi[r * T + t] = c.hi;
+  }
+  const LinkMasks m = link_classify(rec_values, rec_dist, attr_const, r, A);
+  const LinkBase base = link_select_base_from(range, pair_a1, pair_a2, NP, rec_part,
+                                              ent_ptr, r, A, m.nd);
+  if (base.n > split_len) split_list[atomicAdd(split_count, 1)] = (int32_t)r;
+}
+
 // Summary counts in one pass: per-record distortion histogram + per
 // (attr, file) aggregates + isolate count (from the entity->record CSR).
-__global__ void summary_counts_kernel(
+// Item block `block` of blockDim.x entities-then-records; block_counts is the
+// block's LDS staging of the n_counts counters.
+DBL_D void summary_counts_block(
     const uint8_t* __restrict__ rec_dist, const int32_t* __restrict__ rec_file,
     const int64_t* __restrict__ ent_rec_ptr, int64_t E, int64_t R, int A, int F,
-    int n_counts,
+    int n_counts, int64_t block, unsigned int* block_counts,
     unsigned long long* __restrict__ counts) {  // [1 + A*F + A+1]: iso, agg, hist
   // stage all counters in LDS: one global atomic per counter per BLOCK
   // (per-element global atomics on ~12 counters serialize at ~11 ns each)
-  extern __shared__ unsigned int block_counts[];
   for (int i = threadIdx.x; i < n_counts; i += blockDim.x) block_counts[i] = 0u;
   __syncthreads();
 
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t idx = block * blockDim.x + threadIdx.x;
   if (idx < E) {
     if (ent_rec_ptr[idx + 1] == ent_rec_ptr[idx]) atomicAdd(&block_counts[0], 1u);
   } else if (idx < E + R) {
@@ -2416,20 +2591,40 @@ __global__ void summary_counts_kernel(
   }
 }
 
+__global__ void summary_counts_kernel(
+    const uint8_t* __restrict__ rec_dist, const int32_t* __restrict__ rec_file,
+    const int64_t* __restrict__ ent_rec_ptr, int64_t E, int64_t R, int A, int F,
+    int n_counts, unsigned long long* __restrict__ counts) {
+  extern __shared__ unsigned int block_counts[];
+  summary_counts_block(rec_dist, rec_file, ent_rec_ptr, E, R, A, F, n_counts,
+                       blockIdx.x, block_counts, counts);
+}
+
 // Pack loglik + counts (+ the sweep's error count, so the host reads one
-// buffer) into the f64 summary buffer (one tiny launch).
-__global__ void summary_finalize_kernel(
+// buffer) into the f64 summary buffer. Item i of `stride` items in all; item
+// 0 sums the 256 log-likelihood slots in index order (the sum is bitwise the
+// same whoever runs it).
+DBL_D void summary_finalize_items(
     const double* __restrict__ loglik, const unsigned long long* __restrict__ counts,
     int n_counts, const int* __restrict__ err,  // [1] or null
+    int i, int stride,
     double* __restrict__ packed) {              // [1 + n_counts (+ 1 with err)]
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) {
     double s = 0.0;
     for (int j = 0; j < 256; ++j) s += loglik[j];
     packed[0] = s;
     if (err) packed[1 + n_counts] = (double)err[0];
   }
-  if (i < n_counts) packed[1 + i] = (double)counts[i];
+  for (int k = i; k < n_counts; k += stride) packed[1 + k] = (double)counts[k];
+}
+
+// (one tiny launch)
+__global__ void summary_finalize_kernel(
+    const double* __restrict__ loglik, const unsigned long long* __restrict__ counts,
+    int n_counts, const int* __restrict__ err, double* __restrict__ packed) {
+  summary_finalize_items(loglik, counts, n_counts, err,
+                         (int)(blockIdx.x * blockDim.x + threadIdx.x),
+                         (int)(gridDim.x * blockDim.x), packed);
 }
 
 // ---------------------------------------------------------------------------
@@ -2603,6 +2798,13 @@ __global__ void kd_descent_kernel(
 //                        KD descent + stable counting sort of the entities by
 //                        partition id (= stable argsort of ent_part), and the
 //                        record remap through the inverse permutation
+// Launches that read nothing of each other share a launch on the single-rank
+// path, whole blocks routed by block index (no block waits for another):
+//   sweep_begin_kernel   posting histogram + counter-block fill + staging copy
+//   resort_hist_counts / resort_scan_scatter / resort_remap_finalize
+//                        the re-sort with the summary counts and pack riding
+//                        in its first and last launch, and the scan of the
+//                        tile histograms in the scatter's prologue
 // ---------------------------------------------------------------------------
 constexpr int GL_THREADS = 1024;  // block (= entity tile) of the scan and re-sort
 constexpr int GL_WAVES = GL_THREADS / WAVE;
@@ -2707,6 +2909,31 @@ __global__ __launch_bounds__(GL_THREADS) void scan_excl_kernel(
       scan_clear4(counts, base + (int64_t)threadIdx.x * 4, n, vec);
 }
 
+// Sweep head: three jobs that read nothing of each other, routed by block
+// index. Blocks [0, n_hist) build the posting histogram; block n_hist copies
+// the sweep's host inputs ({seed, iteration} and theta) from their pinned
+// host staging words, which the device reads through the same pointer; the
+// blocks after it zero the sweep's counter block, four words a thread.
+__global__ __launch_bounds__(PB_THREADS) void sweep_begin_kernel(
+    const int32_t* __restrict__ ent_part, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ pair_a1, const int32_t* __restrict__ pair_a2,
+    const int32_t* __restrict__ pair_v2, int64_t E, int A, int NP, int64_t Vmax,
+    int32_t* __restrict__ counts, unsigned n_hist,
+    int32_t* __restrict__ zero_blk, int64_t zero_n, bool zero_vec,
+    const uint32_t* __restrict__ stage_pin, uint32_t* __restrict__ stage,
+    int stage_words) {
+  if (blockIdx.x < n_hist) {
+    postings_hist_block(ent_part, ent_values, pair_a1, pair_a2, pair_v2, E, A, NP,
+                        Vmax, counts);
+  } else if (blockIdx.x == n_hist) {
+    for (int i = threadIdx.x; i < stage_words; i += PB_THREADS) stage[i] = stage_pin[i];
+  } else {
+    scan_clear4(zero_blk,
+                ((int64_t)(blockIdx.x - n_hist - 1) * PB_THREADS + threadIdx.x) * 4,
+                zero_n, zero_vec);
+  }
+}
+
 // Count pass: records per entity, observed values per (entity, attribute),
 // and the store of the new links into the state's rec_ent.
 __global__ void csr_count_kernel(
@@ -2800,14 +3027,14 @@ __global__ __launch_bounds__(CSR_ORDER_THREADS) void csr_order_kernel(
 // Re-sort pass 1: KD descent of one tile of GL_THREADS entities and the
 // tile's partition histogram, stored partition-major so one flat exclusive
 // scan gives every (partition, tile) its first output slot.
-__global__ __launch_bounds__(GL_THREADS) void resort_hist_kernel(
+// Tile blockIdx.x; h is the block's LDS table of P counters.
+DBL_D void resort_hist_block(
     const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
     const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
     const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
-    int64_t E, int A, int P, int64_t n_tiles,
+    int64_t E, int A, int P, int64_t n_tiles, int32_t* h,
     int32_t* __restrict__ ent_part_new,  // [E] unsorted new partition ids
     int32_t* __restrict__ hist) {        // [P * n_tiles]
-  __shared__ int32_t h[RESORT_MAX_PARTS];
   for (int i = threadIdx.x; i < P; i += GL_THREADS) h[i] = 0;
   __syncthreads();
   const int64_t e = (int64_t)blockIdx.x * GL_THREADS + threadIdx.x;
@@ -2824,20 +3051,102 @@ __global__ __launch_bounds__(GL_THREADS) void resort_hist_kernel(
     hist[(int64_t)i * n_tiles + blockIdx.x] = h[i];
 }
 
-// Re-sort pass 2 (after the scan of hist): stable scatter. An entity's slot
-// is its (partition, tile) base + same-partition entities of earlier waves in
-// the tile + earlier lanes of its wave, i.e. entity order within a partition
-// is kept. Also emits the next sweep's partition offsets.
-__global__ __launch_bounds__(GL_THREADS) void resort_scatter_kernel(
+__global__ __launch_bounds__(GL_THREADS) void resort_hist_kernel(
+    const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
+    const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
+    const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
+    int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ ent_part_new, int32_t* __restrict__ hist) {
+  __shared__ int32_t h[RESORT_MAX_PARTS];
+  resort_hist_block(ent_values, node_kind, node_attr, node_a, node_b, rset, E, A, P,
+                    n_tiles, h, ent_part_new, hist);
+}
+
+// Sweep tail, launch 1: the re-sort's tile histograms (blocks [0, n_tiles))
+// and the summary counts (the blocks after them), which read nothing the
+// re-sort writes. The two bodies share the block's LDS table.
+__global__ __launch_bounds__(GL_THREADS) void resort_hist_counts_kernel(
+    const int32_t* __restrict__ ent_values, const int32_t* __restrict__ node_kind,
+    const int32_t* __restrict__ node_attr, const int32_t* __restrict__ node_a,
+    const int32_t* __restrict__ node_b, const int32_t* __restrict__ rset,
+    int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ ent_part_new, int32_t* __restrict__ hist,
+    const uint8_t* __restrict__ rec_dist, const int32_t* __restrict__ rec_file,
+    const int64_t* __restrict__ ent_rec_ptr, int64_t R, int F, int n_counts,
+    unsigned long long* __restrict__ counts) {
+  extern __shared__ unsigned int tail_lds[];  // max(P, n_counts) words
+  if ((int64_t)blockIdx.x < n_tiles) {
+    resort_hist_block(ent_values, node_kind, node_attr, node_a, node_b, rset, E, A, P,
+                      n_tiles, reinterpret_cast<int32_t*>(tail_lds), ent_part_new,
+                      hist);
+  } else {
+    summary_counts_block(rec_dist, rec_file, ent_rec_ptr, E, R, A, F, n_counts,
+                         (int64_t)blockIdx.x - n_tiles, tail_lds, counts);
+  }
+}
+
+// The scatter computes the scan of hist itself while it fits one tile of the
+// scan (RESORT_SCAN_MAX counters): every block repeats the few-KiB prefix in
+// LDS instead of waiting on a one-block launch for it.
+constexpr int RESORT_SCAN_MAX = GL_THREADS * 4;
+
+// Re-sort pass 2 (after the scan of hist, or with PROLOGUE doing that scan):
+// stable scatter. An entity's slot is its (partition, tile) base +
+// same-partition entities of earlier waves in the tile + earlier lanes of its
+// wave, i.e. entity order within a partition is kept. Also emits the next
+// sweep's partition offsets. With PROLOGUE tile_base is an output, stored by
+// block 0 exactly as scan_excl would (the counters sum to at most E, so the
+// prefix is exact in int32).
+template <bool PROLOGUE>
+DBL_D void resort_scatter_block(
     const int32_t* __restrict__ ent_part_new, const int32_t* __restrict__ ent_values,
-    const int64_t* __restrict__ tile_base,  // [P * n_tiles + 1] scanned hist
+    const int32_t* __restrict__ hist,  // [P * n_tiles] (PROLOGUE only)
+    bool vec,                          // hist 16-byte aligned
+    int64_t* tile_base,                // [P * n_tiles + 1] scanned hist
     int64_t E, int A, int P, int64_t n_tiles,
     int32_t* __restrict__ out_part,     // [E]
     int32_t* __restrict__ out_values,   // [E, A]
     int32_t* __restrict__ inv,          // [E] old index -> new index
     int64_t* __restrict__ ent_ptr) {    // [P + 1]
   __shared__ int32_t wave_cnt[GL_WAVES * RESORT_MAX_PARTS];
+  __shared__ int32_t base[PROLOGUE ? RESORT_SCAN_MAX : 1];
+  __shared__ int32_t wave_tot[GL_WAVES];
   for (int i = threadIdx.x; i < GL_WAVES * P; i += GL_THREADS) wave_cnt[i] = 0;
+  if (PROLOGUE) {
+    const int64_t n = (int64_t)P * n_tiles;  // <= RESORT_SCAN_MAX
+    const int64_t i0 = (int64_t)threadIdx.x * 4;
+    int32_t c[4];
+    scan_load4(hist, i0, n, vec, c);
+    const int32_t mine = c[0] + c[1] + c[2] + c[3];
+    int32_t inc = mine;  // inclusive scan across the wave
+#pragma unroll
+    for (int off = 1; off < WAVE; off <<= 1) {
+      const int32_t o = __shfl_up(inc, off);
+      if ((int)(threadIdx.x & (WAVE - 1)) >= off) inc += o;
+    }
+    if ((threadIdx.x & (WAVE - 1)) == WAVE - 1) wave_tot[threadIdx.x / WAVE] = inc;
+    __syncthreads();
+    int32_t before = 0, total = 0;
+#pragma unroll
+    for (int w = 0; w < GL_WAVES; ++w) {
+      const int32_t t = wave_tot[w];
+      if (w < (int)(threadIdx.x / WAVE)) before += t;
+      total += t;
+    }
+    int32_t x[4];
+    x[0] = before + inc - mine;
+    x[1] = x[0] + c[0];
+    x[2] = x[1] + c[1];
+    x[3] = x[2] + c[2];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) base[i0 + j] = x[j];
+    if (blockIdx.x == 0) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i0 + j < n) tile_base[i0 + j] = x[j];
+      if (threadIdx.x == 0) tile_base[n] = total;
+    }
+  }
   __syncthreads();
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
@@ -2858,26 +3167,75 @@ __global__ __launch_bounds__(GL_THREADS) void resort_scatter_kernel(
   if (p >= 0) {
     int before = 0;
     for (int w = 0; w < wave; ++w) before += wave_cnt[w * P + p];
-    const int64_t dst = tile_base[(int64_t)p * n_tiles + blockIdx.x] + before + rank;
+    const int64_t slot = (int64_t)p * n_tiles + blockIdx.x;
+    const int64_t dst = (PROLOGUE ? (int64_t)base[slot] : tile_base[slot]) + before + rank;
     out_part[dst] = p;
     for (int a = 0; a < A; ++a) out_values[dst * A + a] = ent_values[e * A + a];
     inv[e] = (int32_t)dst;
   }
-  if (blockIdx.x == 0 && threadIdx.x <= P)
+  if (blockIdx.x == 0 && threadIdx.x <= P) {
+    const int64_t first = (int64_t)threadIdx.x * n_tiles;
     ent_ptr[threadIdx.x] =
-        threadIdx.x < P ? tile_base[(int64_t)threadIdx.x * n_tiles] : E;
+        threadIdx.x < P ? (PROLOGUE ? (int64_t)base[first] : tile_base[first]) : E;
+  }
+}
+
+__global__ __launch_bounds__(GL_THREADS) void resort_scatter_kernel(
+    const int32_t* __restrict__ ent_part_new, const int32_t* __restrict__ ent_values,
+    const int64_t* __restrict__ tile_base, int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ out_part, int32_t* __restrict__ out_values,
+    int32_t* __restrict__ inv, int64_t* __restrict__ ent_ptr) {
+  resort_scatter_block<false>(ent_part_new, ent_values, nullptr, false,
+                              const_cast<int64_t*>(tile_base), E, A, P, n_tiles,
+                              out_part, out_values, inv, ent_ptr);
+}
+
+__global__ __launch_bounds__(GL_THREADS) void resort_scan_scatter_kernel(
+    const int32_t* __restrict__ ent_part_new, const int32_t* __restrict__ ent_values,
+    const int32_t* __restrict__ hist, bool vec, int64_t* __restrict__ tile_base,
+    int64_t E, int A, int P, int64_t n_tiles,
+    int32_t* __restrict__ out_part, int32_t* __restrict__ out_values,
+    int32_t* __restrict__ inv, int64_t* __restrict__ ent_ptr) {
+  resort_scatter_block<true>(ent_part_new, ent_values, hist, vec, tile_base, E, A, P,
+                             n_tiles, out_part, out_values, inv, ent_ptr);
 }
 
 // Re-sort pass 3: records stay put; their links follow the permutation.
-__global__ void resort_remap_kernel(
+DBL_D void resort_remap_item(
     const int64_t* __restrict__ rec_ent, const int32_t* __restrict__ inv,
-    const int32_t* __restrict__ ent_part_new, int64_t R,
+    const int32_t* __restrict__ ent_part_new, int64_t R, int64_t r,
     int64_t* __restrict__ out_rec_ent, int32_t* __restrict__ out_rec_part) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= R) return;
   const int64_t e = rec_ent[r];
   out_rec_ent[r] = inv[e];
   out_rec_part[r] = ent_part_new[e];
+}
+
+__global__ void resort_remap_kernel(
+    const int64_t* __restrict__ rec_ent, const int32_t* __restrict__ inv,
+    const int32_t* __restrict__ ent_part_new, int64_t R,
+    int64_t* __restrict__ out_rec_ent, int32_t* __restrict__ out_rec_part) {
+  resort_remap_item(rec_ent, inv, ent_part_new, R,
+                    (int64_t)blockIdx.x * blockDim.x + threadIdx.x, out_rec_ent,
+                    out_rec_part);
+}
+
+// Sweep tail, launch 3: block 0 packs the summary (summary_finalize's work,
+// which the remap neither feeds nor reads); the blocks after it remap.
+__global__ void resort_remap_finalize_kernel(
+    const int64_t* __restrict__ rec_ent, const int32_t* __restrict__ inv,
+    const int32_t* __restrict__ ent_part_new, int64_t R,
+    int64_t* __restrict__ out_rec_ent, int32_t* __restrict__ out_rec_part,
+    const double* __restrict__ loglik, const unsigned long long* __restrict__ counts,
+    int n_counts, const int* __restrict__ err, double* __restrict__ packed) {
+  if (blockIdx.x == 0) {
+    summary_finalize_items(loglik, counts, n_counts, err, (int)threadIdx.x,
+                           (int)blockDim.x, packed);
+  } else {
+    resort_remap_item(rec_ent, inv, ent_part_new, R,
+                      (int64_t)(blockIdx.x - 1) * blockDim.x + threadIdx.x,
+                      out_rec_ent, out_rec_part);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -3437,6 +3795,48 @@ void link_update(
                     torch::Tensor(), torch::Tensor(), 0, 0);
 }
 
+// The link phase in one launch, for a split list that the previous launch
+// completed (postings_scatter_ranges_split with the same split_len > 0):
+// split_grid blocks serve the list, the wave blocks skip the listed records.
+void link_update_merged(
+    torch::Tensor rec_values, torch::Tensor rec_dist, torch::Tensor rec_gid,
+    torch::Tensor rec_part, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor postings, torch::Tensor ent_values, torch::Tensor ent_ptr,
+    torch::Tensor log_norm, torch::Tensor voff, torch::Tensor csr_row_ptr,
+    torch::Tensor csr_col, torch::Tensor csr_sim, torch::Tensor attr_const,
+    int64_t seed, int64_t iteration, torch::Tensor rec_ent_out,
+    torch::Tensor rec_ent_in, torch::Tensor error_count, torch::Tensor ctrl,
+    torch::Tensor pair_a1, torch::Tensor pair_a2, torch::Tensor split_list,
+    torch::Tensor split_count, int64_t split_len, int64_t split_grid) {
+  const LinkArgs L = make_link_args(
+      rec_values, rec_dist, rec_gid, rec_part, ent_values, ent_ptr, log_norm,
+      voff, csr_row_ptr, csr_col, csr_sim, attr_const, seed, iteration, ctrl,
+      rec_ent_out, rec_ent_in, error_count);
+  if (L.R == 0) return;
+  CHECK_GPU(split_list);
+  CHECK_GPU(split_count);
+  TORCH_CHECK(split_len > 0, "link_update_merged needs split_len > 0");
+  TORCH_CHECK(split_list.scalar_type() == torch::kInt32 &&
+                  split_count.scalar_type() == torch::kInt32,
+              "split_list and split_count must be int32");
+  TORCH_CHECK(split_list.numel() >= L.R && split_count.numel() >= 1 &&
+                  L.R <= INT32_MAX,
+              "split_list holds R records, split_count one counter");
+  TORCH_CHECK(split_grid >= 1 && split_grid <= 65535, "split_grid out of range");
+  const int64_t n_wave = wave_grid(L.R, LINK_SPLIT_WAVES);
+  hipLaunchKernelGGL(link_update_merged_kernel, dim3((unsigned)(split_grid + n_wave)),
+                     dim3(LINK_SPLIT_THREADS), 0, at::cuda::getCurrentCUDAStream(),
+                     split_list.data_ptr<int32_t>(), split_count.data_ptr<int>(),
+                     L.rec_values, L.rec_dist, L.rec_gid, L.rec_part,
+                     cand_lo.data_ptr<int64_t>(), cand_hi.data_ptr<int64_t>(),
+                     postings.data_ptr<int32_t>(), L.ent_values, L.ent_ptr,
+                     L.log_norm, L.voff, L.csr_row_ptr, L.csr_col, L.csr_sim,
+                     L.attr_const, pair_a1.data_ptr<int32_t>(),
+                     pair_a2.data_ptr<int32_t>(), (int)pair_a1.numel(), L.R, L.A,
+                     L.seed, L.iteration, L.ctrl, L.rec_ent_out, L.rec_ent_in,
+                     L.error_count, L.simh_on, split_len, (unsigned)split_grid);
+}
+
 void postings_hist(torch::Tensor ent_part, torch::Tensor ent_values,
                    torch::Tensor pair_a1, torch::Tensor pair_a2,
                    torch::Tensor pair_v2, int64_t Vmax, torch::Tensor counts) {
@@ -3453,6 +3853,51 @@ void postings_hist(torch::Tensor ent_part, torch::Tensor ent_values,
                      pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
                      pair_v2.data_ptr<int32_t>(), E, A, NP, Vmax,
                      counts.data_ptr<int32_t>());
+}
+
+// Sweep head in one launch: postings_hist into counts, zero_blk (int32) all
+// zero, and stage (device) = stage_pin (pinned host memory, same byte count,
+// whole 32-bit words).
+void sweep_begin(torch::Tensor ent_part, torch::Tensor ent_values,
+                 torch::Tensor pair_a1, torch::Tensor pair_a2,
+                 torch::Tensor pair_v2, int64_t Vmax, torch::Tensor counts,
+                 torch::Tensor zero_blk, torch::Tensor stage_pin,
+                 torch::Tensor stage) {
+  CHECK_GPU(ent_values);
+  CHECK_GPU(zero_blk);
+  CHECK_GPU(stage);
+  CHECK_CONTIG(zero_blk);
+  CHECK_CONTIG(stage_pin);
+  CHECK_CONTIG(stage);
+  const int64_t E = ent_values.size(0);
+  const int A = (int)ent_values.size(1);
+  const int NP = (int)pair_a1.numel();
+  const int64_t n = E * (A + NP);
+  TORCH_CHECK(counts.numel() <= INT32_MAX, "dense key space exceeds int32");
+  TORCH_CHECK(zero_blk.scalar_type() == torch::kInt32, "sweep_begin: zero_blk int32");
+  TORCH_CHECK(!stage_pin.is_cuda() && stage_pin.is_pinned(),
+              "sweep_begin: stage_pin must be pinned host memory");
+  const int64_t stage_bytes = stage.numel() * stage.element_size();
+  TORCH_CHECK(stage_pin.numel() * stage_pin.element_size() == stage_bytes &&
+                  stage_bytes % 4 == 0 && stage_bytes / 4 <= INT32_MAX &&
+                  (reinterpret_cast<uintptr_t>(stage.data_ptr()) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(stage_pin.data_ptr()) & 3) == 0,
+              "sweep_begin: stage buffers must be equal-sized runs of 32-bit words");
+  const int64_t n_hist = (n + PB_THREADS - 1) / PB_THREADS;
+  const int64_t zero_n = zero_blk.numel();
+  const int64_t n_zero = (zero_n + 4 * PB_THREADS - 1) / (4 * PB_THREADS);
+  TORCH_CHECK(n_hist + 1 + n_zero <= INT32_MAX, "sweep_begin: grid out of range");
+  const bool zero_vec = (reinterpret_cast<uintptr_t>(zero_blk.data_ptr()) & 15) == 0;
+  hipLaunchKernelGGL(sweep_begin_kernel, dim3((unsigned)(n_hist + 1 + n_zero)),
+                     dim3(PB_THREADS), 0, at::cuda::getCurrentCUDAStream(),
+                     ent_part.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
+                     pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
+                     pair_v2.data_ptr<int32_t>(), E, A, NP, Vmax,
+                     counts.data_ptr<int32_t>(), (unsigned)n_hist,
+                     zero_blk.data_ptr<int32_t>(), zero_n, zero_vec,
+                     static_cast<const uint32_t*>(stage_pin.data_ptr()),
+                     static_cast<uint32_t*>(stage.data_ptr()),
+                     (int)(stage_bytes / 4));
 }
 
 void postings_scatter(torch::Tensor ent_part, torch::Tensor ent_values,
@@ -3609,13 +4054,15 @@ void cand_ranges(torch::Tensor rec_part, torch::Tensor rec_values,
 }
 
 // postings_scatter and cand_ranges as one launch (same results as the pair).
-void postings_scatter_ranges(torch::Tensor ent_part, torch::Tensor ent_values,
-                             torch::Tensor rec_part, torch::Tensor rec_values,
-                             torch::Tensor pair_a1, torch::Tensor pair_a2,
-                             torch::Tensor pair_v2, int64_t Vmax,
-                             torch::Tensor cursor, torch::Tensor ptr,
-                             torch::Tensor postings, torch::Tensor cand_lo,
-                             torch::Tensor cand_hi) {
+// split_len < 0: scatter and ranges only. Otherwise the launch also builds the
+// link phase's split list (postings_scatter_ranges_split_kernel).
+static void postings_scatter_ranges_run(
+    torch::Tensor ent_part, torch::Tensor ent_values, torch::Tensor rec_part,
+    torch::Tensor rec_values, torch::Tensor pair_a1, torch::Tensor pair_a2,
+    torch::Tensor pair_v2, int64_t Vmax, torch::Tensor cursor, torch::Tensor ptr,
+    torch::Tensor postings, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor rec_dist, torch::Tensor attr_const, torch::Tensor ent_ptr,
+    torch::Tensor split_list, torch::Tensor split_count, int64_t split_len) {
   CHECK_GPU(ent_values);
   CHECK_CONTIG(ent_values);
   CHECK_CONTIG(rec_values);
@@ -3632,20 +4079,79 @@ void postings_scatter_ranges(torch::Tensor ent_part, torch::Tensor ent_values,
               ptr.numel() == cursor.numel() + 1,
               "postings_scatter_ranges: shape mismatch");
   TORCH_CHECK(cursor.numel() <= INT32_MAX, "dense key space exceeds int32");
+  const bool with_list = split_len >= 0;
   const int64_t n_scatter = (E * T + PB_THREADS - 1) / PB_THREADS;
-  const int64_t n_ranges = (R * T + PB_THREADS - 1) / PB_THREADS;
+  const int64_t n_ranges = ((with_list ? R : R * T) + PB_THREADS - 1) / PB_THREADS;
   if (n_scatter + n_ranges == 0) return;
   TORCH_CHECK(n_scatter + n_ranges <= INT32_MAX, "postings_scatter_ranges: grid too large");
-  hipLaunchKernelGGL(postings_scatter_ranges_kernel,
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (!with_list) {
+    hipLaunchKernelGGL(postings_scatter_ranges_kernel,
+                       dim3((unsigned)(n_scatter + n_ranges)), dim3(PB_THREADS), 0,
+                       stream,
+                       ent_part.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
+                       rec_part.data_ptr<int32_t>(), rec_values.data_ptr<int32_t>(),
+                       pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
+                       pair_v2.data_ptr<int32_t>(), ptr.data_ptr<int64_t>(), E, R, A,
+                       NP, Vmax, (unsigned)n_scatter, cursor.data_ptr<int32_t>(),
+                       postings.data_ptr<int32_t>(), cand_lo.data_ptr<int64_t>(),
+                       cand_hi.data_ptr<int64_t>());
+    return;
+  }
+  CHECK_GPU(split_list);
+  CHECK_GPU(split_count);
+  CHECK_CONTIG(rec_dist);
+  TORCH_CHECK(A <= MAX_ATTRS, "at most ", MAX_ATTRS, " matching attributes supported");
+  TORCH_CHECK(split_list.scalar_type() == torch::kInt32 &&
+                  split_count.scalar_type() == torch::kInt32,
+              "split_list and split_count must be int32");
+  TORCH_CHECK(split_list.numel() >= R && split_count.numel() >= 1 && R <= INT32_MAX,
+              "split_list holds R records, split_count one counter");
+  TORCH_CHECK(rec_dist.numel() == R * A && attr_const.numel() == A &&
+                  ent_ptr.scalar_type() == torch::kInt64,
+              "postings_scatter_ranges_split: shape mismatch");
+  hipLaunchKernelGGL(postings_scatter_ranges_split_kernel,
                      dim3((unsigned)(n_scatter + n_ranges)), dim3(PB_THREADS), 0,
-                     at::cuda::getCurrentCUDAStream(),
+                     stream,
                      ent_part.data_ptr<int32_t>(), ent_values.data_ptr<int32_t>(),
                      rec_part.data_ptr<int32_t>(), rec_values.data_ptr<int32_t>(),
                      pair_a1.data_ptr<int32_t>(), pair_a2.data_ptr<int32_t>(),
                      pair_v2.data_ptr<int32_t>(), ptr.data_ptr<int64_t>(), E, R, A,
                      NP, Vmax, (unsigned)n_scatter, cursor.data_ptr<int32_t>(),
                      postings.data_ptr<int32_t>(), cand_lo.data_ptr<int64_t>(),
-                     cand_hi.data_ptr<int64_t>());
+                     cand_hi.data_ptr<int64_t>(), rec_dist.data_ptr<uint8_t>(),
+                     attr_const.data_ptr<uint8_t>(), ent_ptr.data_ptr<int64_t>(),
+                     split_len, split_list.data_ptr<int32_t>(),
+                     split_count.data_ptr<int>());
+}
+
+void postings_scatter_ranges(torch::Tensor ent_part, torch::Tensor ent_values,
+                             torch::Tensor rec_part, torch::Tensor rec_values,
+                             torch::Tensor pair_a1, torch::Tensor pair_a2,
+                             torch::Tensor pair_v2, int64_t Vmax,
+                             torch::Tensor cursor, torch::Tensor ptr,
+                             torch::Tensor postings, torch::Tensor cand_lo,
+                             torch::Tensor cand_hi) {
+  postings_scatter_ranges_run(ent_part, ent_values, rec_part, rec_values, pair_a1,
+                              pair_a2, pair_v2, Vmax, cursor, ptr, postings, cand_lo,
+                              cand_hi, {}, {}, {}, {}, {}, -1);
+}
+
+// postings_scatter_ranges plus the split list of link_update_merged: record r
+// is listed when its base list is longer than split_len (>= 0). split_count
+// must be zero on entry.
+void postings_scatter_ranges_split(
+    torch::Tensor ent_part, torch::Tensor ent_values, torch::Tensor rec_part,
+    torch::Tensor rec_values, torch::Tensor pair_a1, torch::Tensor pair_a2,
+    torch::Tensor pair_v2, int64_t Vmax, torch::Tensor cursor, torch::Tensor ptr,
+    torch::Tensor postings, torch::Tensor cand_lo, torch::Tensor cand_hi,
+    torch::Tensor rec_dist, torch::Tensor attr_const, torch::Tensor ent_ptr,
+    torch::Tensor split_list, torch::Tensor split_count, int64_t split_len) {
+  TORCH_CHECK(split_len >= 0, "postings_scatter_ranges_split: split_len >= 0");
+  postings_scatter_ranges_run(ent_part, ent_values, rec_part, rec_values, pair_a1,
+                              pair_a2, pair_v2, Vmax, cursor, ptr, postings, cand_lo,
+                              cand_hi, rec_dist, attr_const, ent_ptr, split_list,
+                              split_count, split_len);
 }
 
 void link_update_dense(
@@ -4170,6 +4676,87 @@ static int64_t resort_tiles(int64_t E) { return (E + GL_THREADS - 1) / GL_THREAD
 // (its scanned bases take one more).
 int64_t resort_hist_size(int64_t E, int64_t P) { return P * resort_tiles(E); }
 
+// The scatter scans the tile histograms in its own prologue while they fit
+// RESORT_SCAN_MAX counters; DBLINK_RESORT_SCAN=0 keeps the scan a launch of
+// its own at every size (A/B; results are identical). Re-read per launch.
+static bool resort_scan_fused() {
+  const char* e = std::getenv("DBLINK_RESORT_SCAN");
+  return e ? std::atoi(e) != 0 : true;
+}
+
+// Operands of the re-sort launches, checked and unpacked in one place.
+struct ResortArgs {
+  int64_t E, R, n_tiles;
+  int A, P;
+};
+
+static ResortArgs make_resort_args(
+    const torch::Tensor& ent_values, const torch::Tensor& ent_part,
+    const torch::Tensor& rec_ent, int64_t P, const torch::Tensor& hist,
+    const torch::Tensor& tile_base, const torch::Tensor& inv,
+    const torch::Tensor& out_ent_part, const torch::Tensor& out_ent_values,
+    const torch::Tensor& out_rec_ent, const torch::Tensor& out_rec_part,
+    const torch::Tensor& ent_ptr) {
+  CHECK_GPU(ent_values);
+  CHECK_CONTIG(ent_values);
+  CHECK_CONTIG(ent_part);
+  CHECK_CONTIG(rec_ent);
+  CHECK_CONTIG(hist);
+  CHECK_CONTIG(tile_base);
+  CHECK_CONTIG(out_ent_part);
+  CHECK_CONTIG(out_ent_values);
+  CHECK_CONTIG(out_rec_ent);
+  CHECK_CONTIG(out_rec_part);
+  ResortArgs r;
+  r.E = ent_values.size(0);
+  r.A = (int)ent_values.size(1);
+  r.R = rec_ent.numel();
+  r.P = (int)P;
+  TORCH_CHECK(P >= 1 && P <= RESORT_MAX_PARTS, "partition_resort supports 1..",
+              RESORT_MAX_PARTS, " partitions");
+  TORCH_CHECK(r.E >= 1 && r.E <= INT32_MAX,
+              "partition_resort: entity count out of range");
+  r.n_tiles = resort_tiles(r.E);
+  TORCH_CHECK(hist.numel() == P * r.n_tiles && tile_base.numel() == P * r.n_tiles + 1 &&
+              inv.numel() == r.E && ent_ptr.numel() == P + 1 &&
+              ent_part.numel() == r.E && out_ent_part.numel() == r.E &&
+              out_ent_values.numel() == r.E * r.A && out_rec_ent.numel() == r.R &&
+              out_rec_part.numel() == r.R,
+              "partition_resort: shape mismatch");
+  TORCH_CHECK(hist.scalar_type() == torch::kInt32 &&
+              tile_base.scalar_type() == torch::kInt64,
+              "partition_resort: hist int32, tile_base int64");
+  return r;
+}
+
+// Scan of hist into tile_base and the stable scatter: one launch while the
+// counters fit the scatter's prologue, the one-block scan and the scatter
+// above that (or with the switch off).
+static void resort_scan_scatter(
+    const ResortArgs& r, torch::Tensor ent_values, torch::Tensor ent_part,
+    torch::Tensor hist, torch::Tensor tile_base, torch::Tensor inv,
+    torch::Tensor out_ent_part, torch::Tensor out_ent_values, torch::Tensor ent_ptr) {
+  auto stream = at::cuda::getCurrentCUDAStream();
+  if (hist.numel() <= RESORT_SCAN_MAX && resort_scan_fused()) {
+    const bool vec = (reinterpret_cast<uintptr_t>(hist.data_ptr()) & 15) == 0;
+    hipLaunchKernelGGL(resort_scan_scatter_kernel, dim3((unsigned)r.n_tiles),
+                       dim3(GL_THREADS), 0, stream, ent_part.data_ptr<int32_t>(),
+                       ent_values.data_ptr<int32_t>(), hist.data_ptr<int32_t>(), vec,
+                       tile_base.data_ptr<int64_t>(), r.E, r.A, r.P, r.n_tiles,
+                       out_ent_part.data_ptr<int32_t>(),
+                       out_ent_values.data_ptr<int32_t>(), inv.data_ptr<int32_t>(),
+                       ent_ptr.data_ptr<int64_t>());
+    return;
+  }
+  scan_excl(hist, tile_base, hist.narrow(0, 0, 0), false);  // no cursor
+  hipLaunchKernelGGL(resort_scatter_kernel, dim3((unsigned)r.n_tiles),
+                     dim3(GL_THREADS), 0, stream, ent_part.data_ptr<int32_t>(),
+                     ent_values.data_ptr<int32_t>(), tile_base.data_ptr<int64_t>(),
+                     r.E, r.A, r.P, r.n_tiles, out_ent_part.data_ptr<int32_t>(),
+                     out_ent_values.data_ptr<int32_t>(), inv.data_ptr<int32_t>(),
+                     ent_ptr.data_ptr<int64_t>());
+}
+
 // KD descent + stable re-sort of the entities by partition id into the other
 // buffer set, the record remap, and the next sweep's partition offsets.
 // ent_part receives the unsorted new partition ids (as kd_descent + copy did).
@@ -4181,47 +4768,81 @@ void partition_resort(
     torch::Tensor out_ent_part, torch::Tensor out_ent_values,
     torch::Tensor out_rec_ent, torch::Tensor out_rec_part,
     torch::Tensor ent_ptr) {
-  CHECK_GPU(ent_values);
-  CHECK_CONTIG(ent_values);
-  CHECK_CONTIG(ent_part);
-  CHECK_CONTIG(rec_ent);
-  CHECK_CONTIG(out_ent_part);
-  CHECK_CONTIG(out_ent_values);
-  CHECK_CONTIG(out_rec_ent);
-  CHECK_CONTIG(out_rec_part);
-  const int64_t E = ent_values.size(0);
-  const int A = (int)ent_values.size(1);
-  const int64_t R = rec_ent.numel();
-  TORCH_CHECK(P >= 1 && P <= RESORT_MAX_PARTS, "partition_resort supports 1..",
-              RESORT_MAX_PARTS, " partitions");
-  TORCH_CHECK(E >= 1 && E <= INT32_MAX, "partition_resort: entity count out of range");
-  const int64_t n_tiles = resort_tiles(E);
-  TORCH_CHECK(hist.numel() == P * n_tiles && tile_base.numel() == P * n_tiles + 1 &&
-              inv.numel() == E && ent_ptr.numel() == P + 1 &&
-              ent_part.numel() == E && out_ent_part.numel() == E &&
-              out_ent_values.numel() == E * A && out_rec_ent.numel() == R &&
-              out_rec_part.numel() == R,
-              "partition_resort: shape mismatch");
+  const ResortArgs r = make_resort_args(ent_values, ent_part, rec_ent, P, hist,
+                                        tile_base, inv, out_ent_part, out_ent_values,
+                                        out_rec_ent, out_rec_part, ent_ptr);
   auto stream = at::cuda::getCurrentCUDAStream();
-  hipLaunchKernelGGL(resort_hist_kernel, dim3((unsigned)n_tiles), dim3(GL_THREADS),
+  hipLaunchKernelGGL(resort_hist_kernel, dim3((unsigned)r.n_tiles), dim3(GL_THREADS),
                      0, stream, ent_values.data_ptr<int32_t>(),
                      node_kind.data_ptr<int32_t>(), node_attr.data_ptr<int32_t>(),
                      node_a.data_ptr<int32_t>(), node_b.data_ptr<int32_t>(),
-                     rset.data_ptr<int32_t>(), E, A, (int)P, n_tiles,
+                     rset.data_ptr<int32_t>(), r.E, r.A, r.P, r.n_tiles,
                      ent_part.data_ptr<int32_t>(), hist.data_ptr<int32_t>());
-  scan_excl(hist, tile_base, hist.narrow(0, 0, 0), false);  // no cursor
-  hipLaunchKernelGGL(resort_scatter_kernel, dim3((unsigned)n_tiles),
-                     dim3(GL_THREADS), 0, stream, ent_part.data_ptr<int32_t>(),
-                     ent_values.data_ptr<int32_t>(), tile_base.data_ptr<int64_t>(),
-                     E, A, (int)P, n_tiles, out_ent_part.data_ptr<int32_t>(),
-                     out_ent_values.data_ptr<int32_t>(), inv.data_ptr<int32_t>(),
-                     ent_ptr.data_ptr<int64_t>());
-  if (R > 0)
-    hipLaunchKernelGGL(resort_remap_kernel, dim3((unsigned)((R + 255) / 256)),
+  resort_scan_scatter(r, ent_values, ent_part, hist, tile_base, inv, out_ent_part,
+                      out_ent_values, ent_ptr);
+  if (r.R > 0)
+    hipLaunchKernelGGL(resort_remap_kernel, dim3((unsigned)((r.R + 255) / 256)),
                        dim3(256), 0, stream, rec_ent.data_ptr<int64_t>(),
-                       inv.data_ptr<int32_t>(), ent_part.data_ptr<int32_t>(), R,
+                       inv.data_ptr<int32_t>(), ent_part.data_ptr<int32_t>(), r.R,
                        out_rec_ent.data_ptr<int64_t>(),
                        out_rec_part.data_ptr<int32_t>());
+}
+
+// Single-rank sweep tail: partition_resort and summary_counts (same operands,
+// same results) in three launches. The summary counts ride with the tile
+// histograms and the summary pack with the record remap: neither reads what
+// the re-sort writes. counts must be zero on entry, as for summary_counts.
+void sweep_tail(
+    torch::Tensor ent_values, torch::Tensor ent_part, torch::Tensor rec_ent,
+    torch::Tensor node_kind, torch::Tensor node_attr, torch::Tensor node_a,
+    torch::Tensor node_b, torch::Tensor rset, int64_t P,
+    torch::Tensor hist, torch::Tensor tile_base, torch::Tensor inv,
+    torch::Tensor out_ent_part, torch::Tensor out_ent_values,
+    torch::Tensor out_rec_ent, torch::Tensor out_rec_part,
+    torch::Tensor ent_ptr, torch::Tensor rec_dist, torch::Tensor rec_file,
+    torch::Tensor ent_rec_ptr, torch::Tensor counts, torch::Tensor loglik,
+    torch::Tensor packed, torch::Tensor err) {
+  const ResortArgs r = make_resort_args(ent_values, ent_part, rec_ent, P, hist,
+                                        tile_base, inv, out_ent_part, out_ent_values,
+                                        out_rec_ent, out_rec_part, ent_ptr);
+  CHECK_CONTIG(rec_dist);
+  CHECK_CONTIG(rec_file);
+  CHECK_CONTIG(ent_rec_ptr);
+  CHECK_CONTIG(counts);
+  const int n_counts = (int)counts.numel();
+  const int F = (n_counts - 1 - (r.A + 1)) / r.A;
+  const bool with_err = err.numel() > 0;
+  TORCH_CHECK(rec_dist.size(0) == r.R && rec_dist.size(1) == r.A &&
+              rec_file.numel() == r.R && ent_rec_ptr.numel() == r.E + 1 &&
+              F >= 1 && n_counts == 1 + r.A * F + r.A + 1 && loglik.numel() >= 256,
+              "sweep_tail: summary shape mismatch");
+  TORCH_CHECK(packed.numel() >= 1 + n_counts + (with_err ? 1 : 0),
+              "packed summary buffer too small");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  const int64_t count_blocks = (r.E + r.R + GL_THREADS - 1) / GL_THREADS;
+  const size_t lds = sizeof(unsigned int) * (size_t)std::max(r.P, n_counts);
+  TORCH_CHECK(lds <= 48 * 1024, "sweep_tail: too many summary counters");
+  hipLaunchKernelGGL(resort_hist_counts_kernel,
+                     dim3((unsigned)(r.n_tiles + count_blocks)), dim3(GL_THREADS), lds,
+                     stream, ent_values.data_ptr<int32_t>(),
+                     node_kind.data_ptr<int32_t>(), node_attr.data_ptr<int32_t>(),
+                     node_a.data_ptr<int32_t>(), node_b.data_ptr<int32_t>(),
+                     rset.data_ptr<int32_t>(), r.E, r.A, r.P, r.n_tiles,
+                     ent_part.data_ptr<int32_t>(), hist.data_ptr<int32_t>(),
+                     rec_dist.data_ptr<uint8_t>(), rec_file.data_ptr<int32_t>(),
+                     ent_rec_ptr.data_ptr<int64_t>(), r.R, F, n_counts,
+                     (unsigned long long*)counts.data_ptr<int64_t>());
+  resort_scan_scatter(r, ent_values, ent_part, hist, tile_base, inv, out_ent_part,
+                      out_ent_values, ent_ptr);
+  hipLaunchKernelGGL(resort_remap_finalize_kernel,
+                     dim3((unsigned)(1 + (r.R + 255) / 256)), dim3(256), 0, stream,
+                     rec_ent.data_ptr<int64_t>(), inv.data_ptr<int32_t>(),
+                     ent_part.data_ptr<int32_t>(), r.R,
+                     out_rec_ent.data_ptr<int64_t>(),
+                     out_rec_part.data_ptr<int32_t>(), loglik.data_ptr<double>(),
+                     (const unsigned long long*)counts.data_ptr<int64_t>(), n_counts,
+                     with_err ? err.data_ptr<int>() : nullptr,
+                     packed.data_ptr<double>());
 }
 
 void kd_descent(
