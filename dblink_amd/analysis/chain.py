@@ -539,9 +539,15 @@ def pairwise_link_probabilities(table, min_probability=0.0, device=None):
     """DataFrame (recordId1, recordId2, probability) of the pairs whose
     posterior link probability is positive and at least ``min_probability``;
     recordId1 < recordId2, rows sorted by (recordId1, recordId2)."""
+    return link_probability_frame(
+        *pairwise_link_counts(table, device=device), min_probability)
+
+
+def link_probability_frame(uniq_ids, a, b, count, S, min_probability=0.0):
+    """The ``pairwise_link_probabilities`` frame from link counts as
+    ``pairwise_link_counts`` (or the online accumulator) returns them."""
     import pandas as pd
 
-    uniq_ids, a, b, count, S = pairwise_link_counts(table, device=device)
     keep = count >= max(1, min_link_count(min_probability, S))
     a, b, count = a[keep], b[keep], count[keep]
     return pd.DataFrame({

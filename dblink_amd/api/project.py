@@ -250,7 +250,8 @@ class Project:
 
 class SampleStep:
     def __init__(self, project, sample_size, burnin_interval=0, thinning_interval=1,
-                 resume=True, sampler="PCG-I", checkpoint_interval=20):
+                 resume=True, sampler="PCG-I", checkpoint_interval=20,
+                 pairwise_link_probabilities=False, min_link_probability=0.0):
         # matching Sampler.scala's require(): a non-positive thinning interval
         # is a config error, not something to silently coerce
         if sample_size <= 0:
@@ -260,6 +261,8 @@ class SampleStep:
         if thinning_interval <= 0:
             raise ValueError("`thinningInterval` must be positive.")
         assert sampler in SUPPORTED_SAMPLERS, f"sampler must be one of {SUPPORTED_SAMPLERS}"
+        if not 0.0 <= float(min_link_probability) <= 1.0:
+            raise ValueError("`minLinkProbability` must lie in [0, 1].")
         self.p = project
         self.sample_size = sample_size
         self.burnin_interval = burnin_interval
@@ -267,6 +270,8 @@ class SampleStep:
         self.resume = resume
         self.sampler = sampler
         self.checkpoint_interval = checkpoint_interval
+        self.pairwise_link_probabilities = bool(pairwise_link_probabilities)
+        self.min_link_probability = float(min_link_probability)
 
     def scale_warning(self, num_records=None):
         """PCG-II / Gibbs-Sequential score every record against every entity
@@ -296,6 +301,11 @@ class SampleStep:
             log.warning(warn)
         state = (self.p.saved_state() if self.resume else None) or self.p.generate_initial_state()
         flags = SamplerFlags.for_sampler(self.sampler)
+        acc = None
+        if self.pairwise_link_probabilities:
+            from ..engine.pair_accumulator import OnlinePairCounts
+
+            acc = OnlinePairCounts()
         sampler_m.sample(
             self.p.engine(),
             state,
@@ -306,14 +316,34 @@ class SampleStep:
             checkpoint_interval=self.checkpoint_interval,
             flags=flags,
             rank=self.p.rank,
+            pair_accumulator=acc,
         )
+        if acc is not None:
+            self._save_link_probabilities(acc)
+
+    def _save_link_probabilities(self, acc):
+        """pairwise-link-probabilities.csv from the counts taken during
+        sampling: the file a summarize step writes from the whole chain."""
+        result = acc.finish(self.p.engine())  # collective; rank 0 holds the merge
+        if self.p.rank == 0:
+            chain_q.save_pairwise_link_probabilities(
+                chain_q.link_probability_frame(
+                    *result, min_probability=self.min_link_probability),
+                self.p.output_path,
+            )
+        comm.barrier()
 
     def mk_string(self):
         mode = "saved state" if self.resume else "new initial state"
+        online = (
+            f"; counting pairwise link probabilities during sampling "
+            f"(minLinkProbability={self.min_link_probability})"
+            if self.pairwise_link_probabilities else ""
+        )
         return (
             f"SampleStep: Evolving the chain from {mode} with sampleSize={self.sample_size}, "
             f"burninInterval={self.burnin_interval}, thinningInterval={self.thinning_interval} "
-            f"and sampler={self.sampler}"
+            f"and sampler={self.sampler}{online}"
         )
 
 
@@ -493,6 +523,9 @@ def parse_steps(config: hocon.Config, project: Project):
                     resume=step.get_or("parameters.resume", True),
                     sampler=step.get_or("parameters.sampler", "PCG-I"),
                     checkpoint_interval=step.get_or("parameters.checkpointInterval", 20),
+                    pairwise_link_probabilities=step.get_or(
+                        "parameters.pairwiseLinkProbabilities", False),
+                    min_link_probability=step.get_or("parameters.minLinkProbability", 0.0),
                 )
             )
         elif name == "evaluate":

@@ -777,6 +777,17 @@ class CpuEngine:
         pid_offsets = np.r_[0, np.cumsum(counts)].astype(np.int64)
         return owned.astype(np.int32), pid_offsets, cluster_offsets, gids
 
+    def accumulate_pairs(self, state: ChainState, acc):
+        """Count this rank's co-clustered record pairs of the current sample
+        into ``acc`` (an ``OnlinePairCounts``): the numpy arm, keys over gids."""
+        from ..analysis import chain as chain_q
+
+        _, _, cluster_offsets, gids = self.linkage_arrays(state)
+        if len(gids) and (gids.min() < 0 or gids.max() > chain_q.MAX_PAIR_IDS):
+            raise ValueError("record gids must lie in [0, 2^31) to be counted as pairs")
+        acc.add_host(*chain_q.pair_counts_from_codes(
+            gids.astype(np.int32), cluster_offsets, device="cpu"))
+
     def linkage_structure(self, state: ChainState, rec_id_of=None):
         """{pid -> list of clusters (lists of record-id strings)} for this rank
         (dict form, used by tests and small runs)."""

@@ -1196,6 +1196,15 @@ class GpuEngine(CpuEngine):
             gids.cpu().numpy(),
         )
 
+    def accumulate_pairs(self, state: ChainState, acc):
+        """Count the current sample's co-clustered pairs from the resident
+        links into ``acc``'s device table. Eager launches on the current
+        stream, between sweeps; the table groups the records itself (the
+        sweep's entity -> records CSR predates the partition re-sort)."""
+        gs = self._gs if self._gs is not None else self._gpu_state(state)
+        acc.device_table(self.device).add_links(
+            gs.rec_ent.contiguous(), gs.rec_gid.contiguous(), gs.E)
+
     def linkage_structure(self, state: ChainState, rec_id_of=None):
         self.sync_state(state)
         return super().linkage_structure(state, rec_id_of)

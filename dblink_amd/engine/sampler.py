@@ -34,6 +34,7 @@ def sample(
     flags: SamplerFlags = None,
     rank=0,
     write_output=True,
+    pair_accumulator=None,
 ):
     if sample_size <= 0:
         raise ValueError("`sampleSize` must be positive.")
@@ -46,6 +47,12 @@ def sample(
     sample_ctr = 0
     initial_iteration = state.iteration
     continue_chain = initial_iteration != 0
+
+    if pair_accumulator is not None and continue_chain and write_output \
+            and pair_accumulator.S == 0:
+        # the counts saved with the state this chain continues from; a
+        # mismatch raises before anything is appended to the chain
+        pair_accumulator.load(output_path, rank, engine.world_size, state.iteration)
 
     linkage_writer = diagnostics_writer = None
     if write_output:
@@ -60,6 +67,15 @@ def sample(
     def sync():
         if hasattr(engine, "sync_state"):
             engine.sync_state(state)
+
+    def save_state():
+        sync()
+        state.save(output_path, rank=rank, world_size=engine.world_size,
+                   extra={"partitioner": engine.partitioner})
+        if pair_accumulator is not None:
+            # next to the state, so both belong to the same iteration
+            pair_accumulator.save(output_path, rank, state.iteration,
+                                  world_size=engine.world_size)
 
     def record_sample():
         nonlocal sample_ctr
@@ -83,6 +99,8 @@ def sample(
                 )
             if diagnostics_writer is not None:
                 diagnostics_writer.write_row(state)
+        if pair_accumulator is not None:
+            pair_accumulator.add_sample(engine, state)
 
     if not continue_chain and burnin_interval == 0:
         record_sample()
@@ -99,9 +117,7 @@ def sample(
             record_sample()
             sample_ctr += 1
         if checkpoint_interval and completed % checkpoint_interval == 0:
-            sync()
-            state.save(output_path, rank=rank, world_size=engine.world_size,
-                       extra={"partitioner": engine.partitioner})
+            save_state()
     dt = time.time() - t0
     iters = state.iteration - initial_iteration
     log.info(
@@ -113,7 +129,5 @@ def sample(
         if diagnostics_writer is not None:
             diagnostics_writer.close()
         comm.barrier()
-        sync()
-        state.save(output_path, rank=rank, world_size=engine.world_size,
-                   extra={"partitioner": engine.partitioner})
+        save_state()
     return state

@@ -294,6 +294,9 @@ void pair_table_add(torch::Tensor codes, torch::Tensor cluster_offsets,
 void pair_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
                        torch::Tensor new_keys, torch::Tensor new_counts,
                        torch::Tensor err);
+void pair_links_csr(torch::Tensor rec_ent, torch::Tensor rec_gid,
+                    torch::Tensor ent_cnt, torch::Tensor ent_ptr,
+                    torch::Tensor codes, torch::Tensor err);
 
 }  // namespace dblink
 
@@ -321,6 +324,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("total_pairs") = -1);
   m.def("pair_table_rehash", &dblink::pair_table_rehash,
         "re-insert a pair-count table's slots into a larger one (gfx950)");
+  m.def("pair_links_csr", &dblink::pair_links_csr,
+        "one sample's links (rec_ent, rec_gid) -> gids grouped by entity and "
+        "their offsets, the input form of pair_table_add (gfx950)",
+        py::arg("rec_ent"), py::arg("rec_gid"), py::arg("ent_cnt"),
+        py::arg("ent_ptr"), py::arg("codes"), py::arg("err"));
   m.def("distortion_update_cpu", &dblink::distortion_update_cpu,
         "distortion resample (OpenMP, bitwise-matches the numpy fast path)");
   m.def("summary_cpu", &dblink::summary_cpu,

@@ -18,6 +18,10 @@
 
 namespace dblink {
 
+// kernels.hip
+void scan_excl(torch::Tensor counts, torch::Tensor ptr, torch::Tensor cursor,
+               bool clear);
+
 namespace {
 
 constexpr unsigned long long PT_EMPTY = ~0ull;
@@ -26,6 +30,8 @@ constexpr int PT_ITEMS = 8;  // consecutive pair indices per thread
 constexpr int64_t PT_TILE = (int64_t)PT_THREADS * PT_ITEMS;
 constexpr int PT_ERR_FULL = 1;    // probed every slot without success
 constexpr int PT_ERR_BOUNDS = 2;  // pair_ptr and cluster_offsets disagree
+constexpr int PT_ERR_LINKS = 4;   // a link's entity or gid is out of range
+constexpr int64_t PT_MAX_CODE = (int64_t)1 << 31;  // codes are < 2^31
 
 DBL_D unsigned long long pt_mix(unsigned long long x) {  // splitmix64 finaliser
   x += 0x9E3779B97F4A7C15ull;
@@ -169,6 +175,63 @@ pair_table_rehash_kernel(const unsigned long long* __restrict__ old_keys,
   }
 }
 
+// ---------------------------------------------------------------------------
+// Links -> member lists. A sample held as a link vector (record r belongs to
+// entity rec_ent[r] and has the global id rec_gid[r]) becomes the
+// (codes, offsets) form pair_table_add_kernel consumes: a counting sort of
+// the gids by entity, as count / scan / scatter. The scan is scan_excl
+// (kernels.hip). An entity without records, or with one, has an empty pair
+// range, so the offsets keep one cluster per entity.
+// ---------------------------------------------------------------------------
+
+// A record is counted only when its entity indexes ent_cnt and its gid fits
+// the 31 bits of a pair key; both kernels apply this test, before any access
+// that depends on e or gid, and skip the same records.
+DBL_D bool pl_valid(int64_t e, int64_t gid, int64_t E) {
+  return e >= 0 && e < E && gid >= 0 && gid < PT_MAX_CODE;
+}
+
+__global__ void __launch_bounds__(PT_THREADS)
+pair_links_count_kernel(const int64_t* __restrict__ rec_ent,
+                        const int64_t* __restrict__ rec_gid, int64_t R, int64_t E,
+                        int32_t* __restrict__ ent_cnt,  // [E], zeroed
+                        int32_t* __restrict__ err) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = rec_ent[r];
+    if (!pl_valid(e, rec_gid[r], E)) {
+      atomicOr(err, PT_ERR_LINKS);
+      continue;
+    }
+    atomicAdd(&ent_cnt[e], 1);
+  }
+}
+
+// cursor [E] is zero on entry (scan_excl cleared the counters it scanned).
+// The slot within the entity's range is whatever the atomic hands out: the
+// member order is arbitrary, which the pair counts do not depend on.
+__global__ void __launch_bounds__(PT_THREADS)
+pair_links_scatter_kernel(const int64_t* __restrict__ rec_ent,
+                          const int64_t* __restrict__ rec_gid, int64_t R, int64_t E,
+                          const int64_t* __restrict__ ent_ptr,  // [E + 1]
+                          int32_t* __restrict__ cursor,
+                          int32_t* __restrict__ codes, int64_t n_codes,
+                          int32_t* __restrict__ err) {
+  for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t e = rec_ent[r];
+    const int64_t gid = rec_gid[r];
+    if (!pl_valid(e, gid, E)) continue;  // flagged by the count pass
+    const int64_t lo = ent_ptr[e], hi = ent_ptr[e + 1];
+    const int64_t pos = atomicAdd(&cursor[e], 1);
+    if (pos < 0 || pos >= hi - lo || lo < 0 || lo + pos >= n_codes) {
+      atomicOr(err, PT_ERR_BOUNDS);  // links changed between the two passes
+      continue;
+    }
+    codes[lo + pos] = (int32_t)gid;
+  }
+}
+
 void check_table(const torch::Tensor& keys, const torch::Tensor& counts,
                  const char* what) {
   TORCH_CHECK(keys.is_cuda() && counts.is_cuda(), what, ": table must be on the GPU");
@@ -227,6 +290,54 @@ void pair_table_add(torch::Tensor codes, torch::Tensor cluster_offsets,
       counts.data_ptr<int32_t>(), (unsigned long long)keys.numel(),
       reinterpret_cast<unsigned long long*>(occupied.data_ptr<int64_t>()),
       err.data_ptr<int32_t>());
+}
+
+// One sample's links -> the member lists pair_table_add takes: codes [R]
+// receives the gids grouped by entity (any order inside an entity), ent_ptr
+// [E + 1] the offsets. ent_cnt [E] is scratch (zeroed here). A
+// record whose entity is outside [0, E) or whose gid is outside [0, 2^31)
+// raises PT_ERR_LINKS in err and is left out; ent_ptr[E] then counts the
+// records that were taken.
+void pair_links_csr(torch::Tensor rec_ent, torch::Tensor rec_gid,
+                    torch::Tensor ent_cnt, torch::Tensor ent_ptr,
+                    torch::Tensor codes, torch::Tensor err) {
+  TORCH_CHECK(rec_ent.is_cuda() && rec_gid.is_cuda() && ent_cnt.is_cuda() &&
+              ent_ptr.is_cuda() && codes.is_cuda() && err.is_cuda(),
+              "pair_links_csr: all tensors must be on the GPU");
+  TORCH_CHECK(rec_ent.is_contiguous() && rec_gid.is_contiguous() &&
+              ent_cnt.is_contiguous() && ent_ptr.is_contiguous() &&
+              codes.is_contiguous(), "pair_links_csr: tensors must be contiguous");
+  TORCH_CHECK(rec_ent.scalar_type() == torch::kInt64 &&
+              rec_gid.scalar_type() == torch::kInt64,
+              "pair_links_csr: rec_ent and rec_gid int64");
+  TORCH_CHECK(ent_cnt.scalar_type() == torch::kInt32 &&
+              ent_ptr.scalar_type() == torch::kInt64 &&
+              codes.scalar_type() == torch::kInt32,
+              "pair_links_csr: ent_cnt and codes int32, ent_ptr int64");
+  TORCH_CHECK(err.scalar_type() == torch::kInt32 && err.numel() == 1,
+              "pair_links_csr: err int32 [1]");
+  const int64_t R = rec_ent.numel(), E = ent_cnt.numel();
+  TORCH_CHECK(rec_ent.dim() == 1 && rec_gid.dim() == 1 && rec_gid.numel() == R,
+              "pair_links_csr: rec_ent and rec_gid must be vectors of one length");
+  TORCH_CHECK(ent_ptr.numel() == E + 1, "pair_links_csr: ent_ptr must hold E + 1 entries");
+  TORCH_CHECK(codes.numel() >= R, "pair_links_csr: codes must hold one entry per record");
+  TORCH_CHECK(R < ((int64_t)1 << 31), "pair_links_csr: at most 2^31 - 1 records");
+  auto stream = at::cuda::getCurrentCUDAStream();
+  ent_cnt.zero_();
+  if (R == 0 || E == 0) {
+    ent_ptr.zero_();
+    return;
+  }
+  const unsigned grid = grid_for((R + PT_THREADS - 1) / PT_THREADS);
+  hipLaunchKernelGGL(pair_links_count_kernel, dim3(grid), dim3(PT_THREADS), 0, stream,
+                     rec_ent.data_ptr<int64_t>(), rec_gid.data_ptr<int64_t>(), R, E,
+                     ent_cnt.data_ptr<int32_t>(), err.data_ptr<int32_t>());
+  // offsets, and the counters zeroed again to serve as the scatter's cursor
+  scan_excl(ent_cnt, ent_ptr, ent_cnt.narrow(0, 0, 0), true);
+  hipLaunchKernelGGL(pair_links_scatter_kernel, dim3(grid), dim3(PT_THREADS), 0, stream,
+                     rec_ent.data_ptr<int64_t>(), rec_gid.data_ptr<int64_t>(), R, E,
+                     ent_ptr.data_ptr<int64_t>(), ent_cnt.data_ptr<int32_t>(),
+                     codes.data_ptr<int32_t>(), codes.numel(), err.data_ptr<int32_t>());
 }
 
 // Re-inserts every occupied slot of the old table, with its count, into the
