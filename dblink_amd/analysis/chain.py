@@ -593,3 +593,169 @@ def read_pairwise_link_probabilities(path):
         "recordId2": np.array(id2, dtype=object),
         "probability": np.array(prob, dtype=np.float64),
     })
+
+
+# ---- most probable clusters from cluster counts -------------------------------
+#
+# Cluster frequencies counted while the chain is sampled (the device
+# ClusterCountTable, or the numpy arm below) instead of from the saved chain.
+# One distinct cluster is one entry of five parallel arrays
+#
+#   keys [n] int64     content key (cluster_keys_numpy), distinct
+#   counts [n] int64   number of samples that contain the cluster
+#   first [n] int64    chain iteration at which it was first seen
+#   offsets [n + 1]    int64 offsets of its members in ``members``
+#   members            int32 gids, in any order inside a cluster
+#
+# As in _mpc_core, a cluster is identified by its 64-bit content key; two
+# different member sets with one key would be counted as one, which is
+# negligible (two independent 64-bit sums plus the size).
+
+CLUSTER_KEY_EMPTY = np.uint64(0xFFFFFFFFFFFFFFFF)  # the tables' free-slot marker
+SMPC_FILE = "shared-most-probable-clusters.csv"
+
+
+def cluster_keys_numpy(gids, offsets):
+    """int64 content keys of the clusters ``gids[offsets[c]:offsets[c + 1]]``:
+    the integers of ``_mpc_keys_numpy`` over the gids, with the all-ones
+    pattern (the device table's EMPTY marker) remapped to 0xFFFF...FE. The
+    device kernel computes the same integers."""
+    off64 = np.asarray(offsets, dtype=np.int64)
+    codes = np.asarray(gids).astype(np.uint64)
+    with np.errstate(over="ignore"):
+        key = _mpc_keys_numpy(codes, off64, np.diff(off64))
+    key = np.asarray(key, dtype=np.uint64).copy()
+    key[key == CLUSTER_KEY_EMPTY] = CLUSTER_KEY_EMPTY - np.uint64(1)
+    return key.view(np.int64)
+
+
+def _empty_cluster_counts():
+    z = np.empty(0, np.int64)
+    return z, z.copy(), z.copy(), np.zeros(1, np.int64), np.empty(0, np.int32)
+
+
+def _gather_segments(starts, sizes):
+    """Indices of the concatenated ranges [starts[i], starts[i] + sizes[i])."""
+    total = int(sizes.sum())
+    out_off = np.zeros(len(sizes) + 1, dtype=np.int64)
+    np.cumsum(sizes, out=out_off[1:])
+    idx = np.arange(total, dtype=np.int64) + np.repeat(starts - out_off[:-1], sizes)
+    return idx, out_off
+
+
+def cluster_counts_of_sample(gids, offsets, iteration):
+    """One sample's clusters as a cluster-count tuple (every count 1, first
+    = ``iteration``); empty clusters are dropped."""
+    offsets = np.asarray(offsets, dtype=np.int64)
+    sizes = np.diff(offsets)
+    keys = cluster_keys_numpy(gids, offsets)
+    keep = sizes > 0
+    idx, out_off = _gather_segments(offsets[:-1][keep], sizes[keep])
+    n = int(keep.sum())
+    part = (keys[keep], np.ones(n, np.int64), np.full(n, int(iteration), np.int64),
+            out_off, np.asarray(gids)[idx].astype(np.int32))
+    return merge_cluster_counts([part])
+
+
+def merge_cluster_counts(parts):
+    """Merge ``(keys, counts, first, offsets, members)`` tuples (the ranks of
+    a run, or a loaded file and the device table) into one, sorted by key:
+    equal keys add their counts, ``first`` becomes the minimum, and the
+    members are taken from one of the parts."""
+    parts = [p for p in parts if len(p[0])]
+    if not parts:
+        return _empty_cluster_counts()
+    keys = np.concatenate([np.asarray(p[0], np.int64) for p in parts])
+    counts = np.concatenate([np.asarray(p[1], np.int64) for p in parts])
+    first = np.concatenate([np.asarray(p[2], np.int64) for p in parts])
+    sizes = np.concatenate([np.diff(np.asarray(p[3], np.int64)) for p in parts])
+    members = np.concatenate([np.asarray(p[4], np.int32) for p in parts])
+    base = np.cumsum([0] + [len(p[4]) for p in parts[:-1]])
+    starts = np.concatenate([np.asarray(p[3], np.int64)[:-1] + b
+                             for p, b in zip(parts, base)])
+    order = np.argsort(keys, kind="stable")
+    keys = keys[order]
+    grp = np.flatnonzero(np.r_[True, keys[1:] != keys[:-1]])
+    rep = order[grp]  # the members of a group's first part stand for all
+    idx, out_off = _gather_segments(starts[rep], sizes[rep])
+    return (keys[grp], np.add.reduceat(counts[order], grp).astype(np.int64),
+            np.minimum.reduceat(first[order], grp).astype(np.int64), out_off,
+            members[idx])
+
+
+def _mpc_best(keys, counts, first, offsets, members):
+    """(gids, cluster index): for every gid in ``members`` (sorted,
+    distinct) the cluster with the largest count, the smallest ``first``
+    among equal counts. The clusters are ranked once (count descending,
+    then ``first`` ascending) and their members laid out in that order, so
+    a gid's winner is its first occurrence: no sort over the members unless
+    the gids are too sparse for a dense position table."""
+    counts, first = np.asarray(counts, np.int64), np.asarray(first, np.int64)
+    offsets = np.asarray(offsets, np.int64)
+    ranked = np.lexsort((first, -counts))
+    sizes = np.diff(offsets)[ranked]
+    idx, _ = _gather_segments(offsets[:-1][ranked], sizes)
+    gid = np.asarray(members)[idx].astype(np.int64)
+    cl = np.repeat(ranked, sizes)
+    n = len(gid)
+    if n == 0:
+        return np.empty(0, np.int64), np.empty(0, np.int64)
+    top = int(gid.max())
+    if top < 4 * n + 1024:
+        # reversed fancy assignment leaves the FIRST occurrence
+        pos = np.full(top + 1, -1, dtype=np.int64)
+        pos[gid[::-1]] = np.arange(n - 1, -1, -1, dtype=np.int64)
+        gids = np.flatnonzero(pos >= 0)
+        return gids, cl[pos[gids]]
+    order = np.argsort(gid, kind="stable")  # keeps the first occurrence first
+    g = gid[order]
+    lead = np.flatnonzero(np.r_[True, g[1:] != g[:-1]])
+    return g[lead], cl[order][lead]
+
+
+def mpc_from_cluster_counts(keys, counts, first, offsets, members, S):
+    """Per record the most probable cluster: ``(gids, best_key, best_count,
+    best_freq)`` with ``best_freq = best_count / S``, gids sorted.
+
+    The winner has the largest count; ties go to the cluster with the
+    smallest ``first``. Two clusters that hold one record cannot first
+    appear in the same iteration, so the winner is unique. This is the tie
+    rule of ``most_probable_clusters`` and ``_mpc_core`` on a chain table
+    whose rows are in iteration order (they keep the cluster met first)."""
+    gids, best = _mpc_best(keys, counts, first, offsets, members)
+    cnt = np.asarray(counts, np.int64)[best]
+    return gids, np.asarray(keys, np.int64)[best], cnt, cnt / S
+
+
+def smpc_from_cluster_counts(keys, counts, first, offsets, members, S, ids=None):
+    """The sMPC estimate as ``save_clusters_csv`` takes it: records grouped
+    by their most probable cluster (tie rule of ``mpc_from_cluster_counts``,
+    equal to ``shared_most_probable_clusters`` on a chain table in
+    iteration order). Members are ``ids[gid]``, or the gids without ``ids``."""
+    gids, best = _mpc_best(keys, counts, first, offsets, members)
+    order = np.argsort(best, kind="stable")
+    sb = best[order]
+    bounds = np.r_[np.flatnonzero(np.r_[True, sb[1:] != sb[:-1]]), len(sb)] \
+        if len(sb) else np.zeros(1, np.int64)
+    names = gids[order].tolist()
+    if ids is not None:
+        names = [ids[g] for g in names]
+    return [set(names[bounds[i]:bounds[i + 1]]) for i in range(len(bounds) - 1)]
+
+
+def mpc_dict(keys, counts, first, offsets, members, S, ids=None):
+    """``{record id: (frozenset of the most probable cluster, frequency)}``,
+    the view ``most_probable_clusters`` gives over a chain table in
+    iteration order (same tie rule, see ``mpc_from_cluster_counts``)."""
+    gids, best = _mpc_best(keys, counts, first, offsets, members)
+    offsets = np.asarray(offsets, np.int64)
+    counts = np.asarray(counts, np.int64)
+    name = (lambda g: int(g)) if ids is None else (lambda g: ids[int(g)])
+    sets, out = {}, {}
+    for g, c in zip(gids.tolist(), best.tolist()):
+        fs = sets.get(c)
+        if fs is None:
+            fs = sets[c] = frozenset(
+                name(m) for m in np.asarray(members)[offsets[c]:offsets[c + 1]].tolist())
+        out[name(g)] = (fs, int(counts[c]) / S)
+    return out

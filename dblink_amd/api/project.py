@@ -251,7 +251,8 @@ class Project:
 class SampleStep:
     def __init__(self, project, sample_size, burnin_interval=0, thinning_interval=1,
                  resume=True, sampler="PCG-I", checkpoint_interval=20,
-                 pairwise_link_probabilities=False, min_link_probability=0.0):
+                 pairwise_link_probabilities=False, min_link_probability=0.0,
+                 shared_most_probable_clusters=False, save_linkage_chain=True):
         # matching Sampler.scala's require(): a non-positive thinning interval
         # is a config error, not something to silently coerce
         if sample_size <= 0:
@@ -263,6 +264,11 @@ class SampleStep:
         assert sampler in SUPPORTED_SAMPLERS, f"sampler must be one of {SUPPORTED_SAMPLERS}"
         if not 0.0 <= float(min_link_probability) <= 1.0:
             raise ValueError("`minLinkProbability` must lie in [0, 1].")
+        if not save_linkage_chain and not (pairwise_link_probabilities
+                                           or shared_most_probable_clusters):
+            raise ValueError(
+                "`saveLinkageChain : false` needs `sharedMostProbableClusters` or "
+                "`pairwiseLinkProbabilities`: the run would produce nothing.")
         self.p = project
         self.sample_size = sample_size
         self.burnin_interval = burnin_interval
@@ -272,6 +278,8 @@ class SampleStep:
         self.checkpoint_interval = checkpoint_interval
         self.pairwise_link_probabilities = bool(pairwise_link_probabilities)
         self.min_link_probability = float(min_link_probability)
+        self.shared_most_probable_clusters = bool(shared_most_probable_clusters)
+        self.save_linkage_chain = bool(save_linkage_chain)
 
     def scale_warning(self, num_records=None):
         """PCG-II / Gibbs-Sequential score every record against every entity
@@ -306,6 +314,14 @@ class SampleStep:
             from ..engine.pair_accumulator import OnlinePairCounts
 
             acc = OnlinePairCounts()
+        extra = {}  # only what is switched on: the defaults call as before
+        cluster_acc = None
+        if self.shared_most_probable_clusters:
+            from ..engine.cluster_accumulator import OnlineClusterCounts
+
+            cluster_acc = extra["cluster_accumulator"] = OnlineClusterCounts()
+        if not self.save_linkage_chain:
+            extra["write_chain"] = False
         sampler_m.sample(
             self.p.engine(),
             state,
@@ -317,9 +333,12 @@ class SampleStep:
             flags=flags,
             rank=self.p.rank,
             pair_accumulator=acc,
+            **extra,
         )
         if acc is not None:
             self._save_link_probabilities(acc)
+        if cluster_acc is not None:
+            self._save_smpc(cluster_acc)
 
     def _save_link_probabilities(self, acc):
         """pairwise-link-probabilities.csv from the counts taken during
@@ -333,6 +352,16 @@ class SampleStep:
             )
         comm.barrier()
 
+    def _save_smpc(self, acc):
+        """shared-most-probable-clusters.csv from the cluster counts taken
+        during sampling: the file a summarize or evaluate step derives from
+        the whole chain."""
+        result = acc.finish(self.p.engine())  # collective; rank 0 holds the merge
+        if self.p.rank == 0:
+            chain_q.save_clusters_csv(
+                result[0], os.path.join(self.p.output_path, chain_q.SMPC_FILE))
+        comm.barrier()
+
     def mk_string(self):
         mode = "saved state" if self.resume else "new initial state"
         online = (
@@ -340,6 +369,10 @@ class SampleStep:
             f"(minLinkProbability={self.min_link_probability})"
             if self.pairwise_link_probabilities else ""
         )
+        if self.shared_most_probable_clusters:
+            online += "; counting the shared most probable clusters during sampling"
+        if not self.save_linkage_chain:
+            online += "; not saving the linkage chain"
         return (
             f"SampleStep: Evolving the chain from {mode} with sampleSize={self.sample_size}, "
             f"burninInterval={self.burnin_interval}, thinningInterval={self.thinning_interval} "
@@ -526,6 +559,9 @@ def parse_steps(config: hocon.Config, project: Project):
                     pairwise_link_probabilities=step.get_or(
                         "parameters.pairwiseLinkProbabilities", False),
                     min_link_probability=step.get_or("parameters.minLinkProbability", 0.0),
+                    shared_most_probable_clusters=step.get_or(
+                        "parameters.sharedMostProbableClusters", False),
+                    save_linkage_chain=step.get_or("parameters.saveLinkageChain", True),
                 )
             )
         elif name == "evaluate":

@@ -788,6 +788,16 @@ class CpuEngine:
         acc.add_host(*chain_q.pair_counts_from_codes(
             gids.astype(np.int32), cluster_offsets, device="cpu"))
 
+    def accumulate_clusters(self, state: ChainState, acc):
+        """Count this rank's clusters of the current sample into ``acc`` (an
+        ``OnlineClusterCounts``): the numpy arm, content keys over gids."""
+        from ..analysis import chain as chain_q
+
+        _, _, cluster_offsets, gids = self.linkage_arrays(state)
+        if len(gids) and (gids.min() < 0 or gids.max() > chain_q.MAX_PAIR_IDS):
+            raise ValueError("record gids must lie in [0, 2^31) to be counted in clusters")
+        acc.add_host(gids, cluster_offsets, state.iteration)
+
     def linkage_structure(self, state: ChainState, rec_id_of=None):
         """{pid -> list of clusters (lists of record-id strings)} for this rank
         (dict form, used by tests and small runs)."""

@@ -1205,6 +1205,14 @@ class GpuEngine(CpuEngine):
         acc.device_table(self.device).add_links(
             gs.rec_ent.contiguous(), gs.rec_gid.contiguous(), gs.E)
 
+    def accumulate_clusters(self, state: ChainState, acc):
+        """Count the current sample's clusters from the resident links into
+        ``acc``'s device table; eager launches between sweeps, as
+        ``accumulate_pairs``."""
+        gs = self._gs if self._gs is not None else self._gpu_state(state)
+        acc.device_table(self.device).add_links(
+            gs.rec_ent.contiguous(), gs.rec_gid.contiguous(), gs.E, state.iteration)
+
     def linkage_structure(self, state: ChainState, rec_id_of=None):
         self.sync_state(state)
         return super().linkage_structure(state, rec_id_of)

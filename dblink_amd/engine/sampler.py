@@ -35,6 +35,8 @@ def sample(
     rank=0,
     write_output=True,
     pair_accumulator=None,
+    cluster_accumulator=None,
+    write_chain=True,
 ):
     if sample_size <= 0:
         raise ValueError("`sampleSize` must be positive.")
@@ -53,12 +55,17 @@ def sample(
         # the counts saved with the state this chain continues from; a
         # mismatch raises before anything is appended to the chain
         pair_accumulator.load(output_path, rank, engine.world_size, state.iteration)
+    if cluster_accumulator is not None and continue_chain and write_output \
+            and cluster_accumulator.S == 0:
+        cluster_accumulator.load(output_path, rank, engine.world_size, state.iteration)
 
     linkage_writer = diagnostics_writer = None
     if write_output:
-        linkage_writer = LinkageChainWriter(
-            output_path, rank=rank, buffer_size=write_buffer_size, append=continue_chain
-        )
+        if write_chain:
+            linkage_writer = LinkageChainWriter(
+                output_path, rank=rank, buffer_size=write_buffer_size,
+                append=continue_chain
+            )
         if rank == 0:
             diagnostics_writer = DiagnosticsWriter(
                 output_path, engine.cache, continue_chain=continue_chain
@@ -76,10 +83,13 @@ def sample(
             # next to the state, so both belong to the same iteration
             pair_accumulator.save(output_path, rank, state.iteration,
                                   world_size=engine.world_size)
+        if cluster_accumulator is not None:
+            cluster_accumulator.save(output_path, rank, state.iteration,
+                                     world_size=engine.world_size)
 
     def record_sample():
         nonlocal sample_ctr
-        if write_output:
+        if linkage_writer is not None:
             pid_list, pid_offsets, cluster_offsets, gids = engine.linkage_arrays(state)
             dictionary = getattr(engine, "rec_ids_array", None)
             if dictionary is not None:
@@ -97,10 +107,12 @@ def sample(
                 linkage_writer.append_arrays(
                     state.iteration, pid_list, pid_offsets, cluster_offsets, record_ids
                 )
-            if diagnostics_writer is not None:
-                diagnostics_writer.write_row(state)
+        if diagnostics_writer is not None:
+            diagnostics_writer.write_row(state)
         if pair_accumulator is not None:
             pair_accumulator.add_sample(engine, state)
+        if cluster_accumulator is not None:
+            cluster_accumulator.add_sample(engine, state)
 
     if not continue_chain and burnin_interval == 0:
         record_sample()
@@ -125,7 +137,8 @@ def sample(
         iters, dt, iters / dt if dt > 0 else float("nan"),
     )
     if write_output:
-        linkage_writer.close()
+        if linkage_writer is not None:
+            linkage_writer.close()
         if diagnostics_writer is not None:
             diagnostics_writer.close()
         comm.barrier()

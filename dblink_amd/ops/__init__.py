@@ -87,6 +87,7 @@ def pair_counts_route(total_pairs, cuda_available):
 
 
 from .pair_table import PairCountTable  # noqa: E402,F401
+from .cluster_table import ClusterCountTable  # noqa: E402,F401
 
 
 def sim_pairs(values, similarity_fn):

@@ -297,6 +297,16 @@ void pair_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
 void pair_links_csr(torch::Tensor rec_ent, torch::Tensor rec_gid,
                     torch::Tensor ent_cnt, torch::Tensor ent_ptr,
                     torch::Tensor codes, torch::Tensor err);
+void cluster_table_add(torch::Tensor codes, torch::Tensor ent_ptr, int64_t iteration,
+                       torch::Tensor keys, torch::Tensor counts, torch::Tensor first,
+                       torch::Tensor size, torch::Tensor off, torch::Tensor members,
+                       torch::Tensor ctr, torch::Tensor err);
+void cluster_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
+                          torch::Tensor old_first, torch::Tensor old_size,
+                          torch::Tensor old_off, torch::Tensor new_keys,
+                          torch::Tensor new_counts, torch::Tensor new_first,
+                          torch::Tensor new_size, torch::Tensor new_off,
+                          torch::Tensor err);
 
 }  // namespace dblink
 
@@ -329,6 +339,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "their offsets, the input form of pair_table_add (gfx950)",
         py::arg("rec_ent"), py::arg("rec_gid"), py::arg("ent_cnt"),
         py::arg("ent_ptr"), py::arg("codes"), py::arg("err"));
+  m.def("cluster_table_add", &dblink::cluster_table_add,
+        "count one sample's clusters (gids grouped by entity, as pair_links_csr "
+        "leaves them) into the cluster-count hash table (gfx950)",
+        py::arg("codes"), py::arg("ent_ptr"), py::arg("iteration"), py::arg("keys"),
+        py::arg("counts"), py::arg("first"), py::arg("size"), py::arg("off"),
+        py::arg("members"), py::arg("ctr"), py::arg("err"));
+  m.def("cluster_table_rehash", &dblink::cluster_table_rehash,
+        "re-insert a cluster-count table's slots, with their metadata, into a "
+        "larger one (gfx950)");
   m.def("distortion_update_cpu", &dblink::distortion_update_cpu,
         "distortion resample (OpenMP, bitwise-matches the numpy fast path)");
   m.def("summary_cpu", &dblink::summary_cpu,

@@ -9,6 +9,10 @@
 // and a chunk is never half-applied. Every probe loop is bounded by the
 // capacity; a thread that runs out of slots raises the error flag and goes
 // on. No loop here waits on another thread's progress.
+//
+// The second half of the file is the cluster-count table (how often each
+// distinct cluster occurs, for the most probable clusters): the same probing
+// over content keys, with per-slot metadata and a member arena.
 
 #include <ATen/cuda/CUDAContext.h>
 #include <hip/hip_runtime.h>
@@ -360,6 +364,240 @@ void pair_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
       reinterpret_cast<unsigned long long*>(new_keys.data_ptr<int64_t>()),
       new_counts.data_ptr<int32_t>(), (unsigned long long)new_keys.numel(),
       err.data_ptr<int32_t>());
+}
+
+// ---------------------------------------------------------------------------
+// Cluster-count table: how often each distinct cluster (member set) occurs
+// over the samples, for the most probable clusters. Same open addressing as
+// above, keyed by an order-independent 64-bit content key, with per-slot
+// metadata (first iteration, size, start of the member list) and one member
+// arena shared by all slots. The host keeps the load <= 0.5 and the arena
+// large enough for one whole sample before every add.
+//
+// Within one sample a record lies in one cluster, so two entities of one
+// launch never claim or match the same slot (up to key collisions): the
+// claimer's plain stores to first/size/off and the arena are not read in the
+// launch that wrote them, only by later launches on the stream.
+// ---------------------------------------------------------------------------
+
+namespace {
+
+constexpr int CT_ERR_ARENA = 8;  // the arena cannot take a new cluster's members
+
+// The integers of chain._mpc_keys_numpy over the gids: two splitmix-derived
+// hashes per member, each summed mod 2^64, combined with the size. EMPTY is
+// remapped so that no cluster looks like a free slot.
+DBL_D unsigned long long ct_key(const int32_t* __restrict__ codes, int64_t lo, int64_t hi) {
+  unsigned long long s1 = 0, s2 = 0;
+  for (int64_t i = lo; i < hi; ++i) {
+    const unsigned long long h1 = pt_mix((unsigned long long)(uint32_t)codes[i]);
+    unsigned long long h2 = (h1 ^ (h1 >> 29)) * 0xD6E8FEB86659FD93ull;
+    h2 ^= h2 >> 32;
+    s1 += h1;
+    s2 += h2;
+  }
+  const unsigned long long key =
+      (s1 ^ (s2 * 0x9E3779B97F4A7C15ull)) + (unsigned long long)(hi - lo);
+  return key == PT_EMPTY ? PT_EMPTY - 1 : key;
+}
+
+// The slot of `key`, claimed on first sight (*claimed = 1), or -1 when all
+// `cap` slots were probed in vain. Probing as pt_insert.
+DBL_D int64_t ct_slot(unsigned long long* __restrict__ keys, unsigned long long cap,
+                      unsigned long long key, int* claimed) {
+  const unsigned long long mask = cap - 1;
+  unsigned long long slot = pt_mix(key) & mask;
+  *claimed = 0;
+  for (unsigned long long n = 0; n < cap; ++n, slot = (slot + 1) & mask) {
+    unsigned long long cur = __atomic_load_n(&keys[slot], __ATOMIC_RELAXED);
+    if (cur == PT_EMPTY) {
+      cur = atomicCAS(&keys[slot], PT_EMPTY, key);
+      if (cur == PT_EMPTY) {
+        *claimed = 1;
+        return (int64_t)slot;
+      }
+    }
+    if (cur == key) return (int64_t)slot;
+  }
+  return -1;
+}
+
+// One thread per entity (grid-stride). ctr[0] counts the occupied slots,
+// ctr[1] is the arena cursor. A launch that finds err already set (a bad
+// link flagged by pair_links_csr) counts nothing.
+__global__ void __launch_bounds__(PT_THREADS)
+cluster_table_add_kernel(const int32_t* __restrict__ codes, int64_t n_codes,
+                         const int64_t* __restrict__ ent_ptr, int64_t E,
+                         int32_t iteration, unsigned long long* __restrict__ keys,
+                         int32_t* __restrict__ counts, int32_t* __restrict__ first,
+                         int32_t* __restrict__ size, int64_t* __restrict__ off,
+                         unsigned long long cap, int32_t* __restrict__ members,
+                         int64_t arena_cap, unsigned long long* __restrict__ ctr,
+                         int32_t* __restrict__ err) {
+  __shared__ int skip;
+  if (threadIdx.x == 0) skip = __atomic_load_n(err, __ATOMIC_RELAXED) != 0;
+  __syncthreads();
+  if (skip) return;  // uniform over the block
+  unsigned int claimed_n = 0;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < E;
+       e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t lo = ent_ptr[e], hi = ent_ptr[e + 1];
+    if (lo == hi) continue;  // an entity without records is no cluster
+    if (lo < 0 || hi < lo || hi > n_codes) {
+      atomicOr(err, PT_ERR_BOUNDS);
+      continue;
+    }
+    const int64_t n = hi - lo;
+    int claimed;
+    const int64_t slot = ct_slot(keys, cap, ct_key(codes, lo, hi), &claimed);
+    if (slot < 0) {
+      atomicOr(err, PT_ERR_FULL);
+      continue;
+    }
+    atomicAdd(&counts[slot], 1);
+    if (!claimed) continue;
+    ++claimed_n;
+    const int64_t o = (int64_t)atomicAdd(&ctr[1], (unsigned long long)n);
+    first[slot] = iteration;
+    if (o < 0 || o + n > arena_cap) {  // the host sized the arena wrongly
+      atomicOr(err, CT_ERR_ARENA);
+      size[slot] = 0;
+      off[slot] = 0;
+      continue;
+    }
+    size[slot] = (int32_t)n;
+    off[slot] = o;
+    for (int64_t i = 0; i < n; ++i) members[o + i] = codes[lo + i];
+  }
+  // one counter update per wave (every lane gets here: no lane leaves the
+  // loop early)
+#pragma unroll
+  for (int s = WAVE / 2; s > 0; s >>= 1) claimed_n += __shfl_down(claimed_n, s);
+  if ((threadIdx.x & (WAVE - 1)) == 0 && claimed_n)
+    atomicAdd(&ctr[0], (unsigned long long)claimed_n);
+}
+
+// Re-inserts the old table's keys and carries count and metadata along; the
+// arena stays where it is.
+__global__ void __launch_bounds__(PT_THREADS)
+cluster_table_rehash_kernel(const unsigned long long* __restrict__ old_keys,
+                            const int32_t* __restrict__ old_counts,
+                            const int32_t* __restrict__ old_first,
+                            const int32_t* __restrict__ old_size,
+                            const int64_t* __restrict__ old_off, int64_t old_cap,
+                            unsigned long long* __restrict__ keys,
+                            int32_t* __restrict__ counts, int32_t* __restrict__ first,
+                            int32_t* __restrict__ size, int64_t* __restrict__ off,
+                            unsigned long long cap, int32_t* __restrict__ err) {
+  for (int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; s < old_cap;
+       s += (int64_t)gridDim.x * blockDim.x) {
+    const unsigned long long key = old_keys[s];
+    if (key == PT_EMPTY) continue;
+    int claimed;
+    const int64_t slot = ct_slot(keys, cap, key, &claimed);
+    if (slot < 0) {
+      atomicOr(err, PT_ERR_FULL);
+      continue;
+    }
+    atomicAdd(&counts[slot], old_counts[s]);
+    if (claimed) {  // old keys are distinct, so every one claims
+      first[slot] = old_first[s];
+      size[slot] = old_size[s];
+      off[slot] = old_off[s];
+    }
+  }
+}
+
+void check_cluster_table(const torch::Tensor& keys, const torch::Tensor& counts,
+                         const torch::Tensor& first, const torch::Tensor& size,
+                         const torch::Tensor& off, const char* what) {
+  check_table(keys, counts, what);
+  const int64_t cap = keys.numel();
+  TORCH_CHECK(first.is_cuda() && size.is_cuda() && off.is_cuda(), what,
+              ": table must be on the GPU");
+  TORCH_CHECK(first.is_contiguous() && size.is_contiguous() && off.is_contiguous(),
+              what, ": table must be contiguous");
+  TORCH_CHECK(first.scalar_type() == torch::kInt32 &&
+              size.scalar_type() == torch::kInt32 &&
+              off.scalar_type() == torch::kInt64, what,
+              ": first and size int32, off int64");
+  TORCH_CHECK(first.numel() == cap && size.numel() == cap && off.numel() == cap,
+              what, ": first, size and off must match keys");
+}
+
+}  // namespace
+
+// Counts one sample's clusters into the cluster-count table. codes and
+// ent_ptr [E + 1] are what pair_links_csr produces: gids grouped by entity.
+// ctr is int64 [2]: occupied slots, arena cursor. The caller guarantees
+// capacity >= 2 (occupied + min(E, R)) and an arena of cursor + R entries.
+void cluster_table_add(torch::Tensor codes, torch::Tensor ent_ptr, int64_t iteration,
+                       torch::Tensor keys, torch::Tensor counts, torch::Tensor first,
+                       torch::Tensor size, torch::Tensor off, torch::Tensor members,
+                       torch::Tensor ctr, torch::Tensor err) {
+  check_cluster_table(keys, counts, first, size, off, "cluster_table_add");
+  TORCH_CHECK(codes.is_cuda() && ent_ptr.is_cuda() && members.is_cuda() &&
+              ctr.is_cuda() && err.is_cuda(),
+              "cluster_table_add: all tensors must be on the GPU");
+  TORCH_CHECK(codes.is_contiguous() && ent_ptr.is_contiguous() &&
+              members.is_contiguous() && ctr.is_contiguous(),
+              "cluster_table_add: tensors must be contiguous");
+  TORCH_CHECK(codes.scalar_type() == torch::kInt32 &&
+              ent_ptr.scalar_type() == torch::kInt64 &&
+              members.scalar_type() == torch::kInt32,
+              "cluster_table_add: codes and members int32, ent_ptr int64");
+  TORCH_CHECK(ctr.scalar_type() == torch::kInt64 && ctr.numel() == 2 &&
+              err.scalar_type() == torch::kInt32 && err.numel() == 1,
+              "cluster_table_add: ctr int64 [2], err int32 [1]");
+  TORCH_CHECK(iteration >= 0 && iteration < PT_MAX_CODE,
+              "cluster_table_add: iteration must lie in [0, 2^31)");
+  TORCH_CHECK(codes.numel() < PT_MAX_CODE,
+              "cluster_table_add: at most 2^31 - 1 records");
+  const int64_t E = ent_ptr.numel() - 1;
+  TORCH_CHECK(E >= 0, "cluster_table_add: ent_ptr must hold E + 1 entries");
+  if (E == 0 || codes.numel() == 0) return;
+  hipLaunchKernelGGL(
+      cluster_table_add_kernel, dim3(grid_for((E + PT_THREADS - 1) / PT_THREADS)),
+      dim3(PT_THREADS), 0, at::cuda::getCurrentCUDAStream(),
+      codes.data_ptr<int32_t>(), codes.numel(), ent_ptr.data_ptr<int64_t>(), E,
+      (int32_t)iteration,
+      reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>()),
+      counts.data_ptr<int32_t>(), first.data_ptr<int32_t>(),
+      size.data_ptr<int32_t>(), off.data_ptr<int64_t>(),
+      (unsigned long long)keys.numel(), members.data_ptr<int32_t>(),
+      members.numel(),
+      reinterpret_cast<unsigned long long*>(ctr.data_ptr<int64_t>()),
+      err.data_ptr<int32_t>());
+}
+
+// Re-inserts every occupied slot of the old table, with its count and
+// metadata, into the new (EMPTY-filled, zero-count) one.
+void cluster_table_rehash(torch::Tensor old_keys, torch::Tensor old_counts,
+                          torch::Tensor old_first, torch::Tensor old_size,
+                          torch::Tensor old_off, torch::Tensor new_keys,
+                          torch::Tensor new_counts, torch::Tensor new_first,
+                          torch::Tensor new_size, torch::Tensor new_off,
+                          torch::Tensor err) {
+  check_cluster_table(old_keys, old_counts, old_first, old_size, old_off,
+                      "cluster_table_rehash (old)");
+  check_cluster_table(new_keys, new_counts, new_first, new_size, new_off,
+                      "cluster_table_rehash (new)");
+  TORCH_CHECK(err.is_cuda() && err.scalar_type() == torch::kInt32 &&
+              err.numel() == 1, "cluster_table_rehash: err int32 [1] on the GPU");
+  TORCH_CHECK(new_keys.data_ptr() != old_keys.data_ptr(),
+              "cluster_table_rehash: tables must differ");
+  const int64_t old_cap = old_keys.numel();
+  hipLaunchKernelGGL(
+      cluster_table_rehash_kernel,
+      dim3(grid_for((old_cap + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0,
+      at::cuda::getCurrentCUDAStream(),
+      reinterpret_cast<const unsigned long long*>(old_keys.data_ptr<int64_t>()),
+      old_counts.data_ptr<int32_t>(), old_first.data_ptr<int32_t>(),
+      old_size.data_ptr<int32_t>(), old_off.data_ptr<int64_t>(), old_cap,
+      reinterpret_cast<unsigned long long*>(new_keys.data_ptr<int64_t>()),
+      new_counts.data_ptr<int32_t>(), new_first.data_ptr<int32_t>(),
+      new_size.data_ptr<int32_t>(), new_off.data_ptr<int64_t>(),
+      (unsigned long long)new_keys.numel(), err.data_ptr<int32_t>());
 }
 
 }  // namespace dblink
